@@ -14,13 +14,27 @@ and input stream from its global index (ol_dsp_amd.workload), so an N-GPU run pr
 the instances a one-GPU run of the same total would.  No data-path collective (weak scaling); one
 RCCL all-reduce after each timed region gathers the counters.
 
-Repetitions ("median of 5"): every leg is built first and kept alive; then each leg
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: it builds
+the one workload, warms it up, times ONE region of exactly N steps, writes the outputs of the last
+timed step when `--dump-outputs DIR` is given, and prints the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the region's roofline).  Everything else below -- the
+repetitions, the `--also` legs, the CPU baselines, the parity replays, the mix's own timing, the
+box's copy rate and the full record (--full-json) -- runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path left in its output buffers after the last timed
+step as DIR/<name>.npy (float32): `out` [channels][frames][instances] and, for voice_poly, `bus`
+[frames][buses].  An array past its share of DUMP_BYTES keeps a fixed sample of its instance
+columns (numpy default_rng(DUMP_SEED), sorted).  Inputs and parameters derive from the global
+instance index and the step number alone, so the same arguments give the same arrays run after run.
+
+Repetitions (`--full`; SURVEY 8d: "median of 5"): every leg is built first and kept alive; then each leg
 runs --reps timed regions of exactly --steps steps (barrier + device sync on both sides, max over
 ranks), the leg order rotated by one leg per repetition, after at least --leg-warmup untimed steps
 before a leg's first region and --rep-warmup before each later one.  Every reported time is the
 median region, with the min-max range beside it.
 
-Prints ONE compact JSON line (rank 0; the whole record, every leg in full, goes to --full-json):
+Prints ONE compact JSON line (rank 0; with --full the whole record, every leg in full, goes to
+--full-json); all but the roofline of the main leg need --full:
   roofline     : algorithmic bytes of the dominant kernel / its HIP-event-timed duration vs 8 TB/s
                  (frac = read+write, frac_read = the read share: the north star's HBM-read roofline)
   cpu_baseline : the CPU oracle (port) or the compiled reference (reference) on all host cores
@@ -60,6 +74,8 @@ VOICE_FLOPS_PER_SAMPLE = 64.0
 # accumulate 3 (x4 = 168) -> 216.
 VOICE_MOOG_FLOPS_PER_SAMPLE = 216.0
 VOICE_KINDS = ("voice", "voice_moog")
+DUMP_BYTES = 32 << 20  # --dump-outputs: bytes written per run, every array and rank together
+DUMP_SEED = 20250    # --dump-outputs: seed of the instance sample of an array past its share
 VOICE_TOL = 1e-5      # max |gpu - ref| / max(|ref|, rms(ref)) per voice (tests/test_gpu_parity.py)
 WORKLOADS = {
     # name: (kind, default instances per GPU, BASELINE config it restates)
@@ -100,8 +116,14 @@ def parse(argv=None):
                     help="ranks (one per GPU); without torchrun, N > 1 launches the N rank processes itself")
     ap.add_argument("--steps", type=int, default=200, help="steps (blocks) in each timed region")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: --reps repetitions, the --also legs, the CPU "
+                         "baselines, the parity replays, the mix's own timing, the copy rate, --full-json")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--reps", type=int, default=5,
-                    help="timed regions per leg (SURVEY 8d: median of 5), leg order rotated between them")
+                    help="--full: timed regions per leg (SURVEY 8d: median of 5), leg order rotated between them "
+                         "(a plain run times one region)")
     ap.add_argument("--leg-warmup", type=int, default=50,
                     help="untimed steps before a leg's first region at least (the sustained clock: "
                          "profiles/r5/chorus_launch_durations.txt)")
@@ -109,20 +131,23 @@ def parse(argv=None):
     ap.add_argument("--workload", default="chorus", choices=sorted(WORKLOADS))
     ap.add_argument("--instances", type=int, default=0, help="instances per GPU (0 = workload default)")
     ap.add_argument("--also", default=None,
-                    help=f"comma list of extra workloads timed in the same run (default for chorus: {DEFAULT_ALSO}; "
+                    help=f"--full: comma list of extra workloads timed in the same run (default for chorus: {DEFAULT_ALSO}; "
                          "'' = none)")
     ap.add_argument("--block", type=int, default=256)
     ap.add_argument("--sample-rate", type=float, default=48000.0)
     ap.add_argument("--pool-bytes", type=float, default=1.0e9, help="bytes of distinct input blocks (> 256 MiB IC)")
-    ap.add_argument("--cpu-seconds", type=float, default=4.0, help="wall budget of each -O2 CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=4.0, help="--full: wall budget of each -O2 CPU baseline (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may run on")
-    ap.add_argument("--no-parity", action="store_true", help="skip the untimed oracle parity check per leg")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the untimed oracle parity check per leg")
     ap.add_argument("--traffic-json", default="", help="PMC traffic summary (tools/pmc_traffic.py)")
-    ap.add_argument("--full-json", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
-                    help="where the full (verbose) record of every leg is written ('' = nowhere)")
+    ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_out", "bench_full.json"),
+                    help="--full: where the full (verbose) record of every leg is written ('' = nowhere)")
     ap.add_argument("--stub", action="store_true",
                     help="CPU launcher check: a no-GPU stand-in leg over gloo (tests/test_bench_launch.py)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:      # a plain run: the main workload, one timed region, no CPU work, no record
+        args.also, args.reps, args.cpu_seconds, args.no_parity, args.full_json = "", 1, 0.0, True, ""
+    return args
 
 
 def _r(x, sig: int = 4):
@@ -601,6 +626,30 @@ class Leg:
         kern_ms = region[0].elapsed_time(region[1]) / steps
         self.reps.append(reduce_stats(RunStats(elapsed, kern_ms, float(self.n) * self.B * steps, 0.0, 1.0), device=dev))
 
+    def dump_outputs(self, d: str) -> dict:
+        """--dump-outputs: what the last step left in the buffers a caller of the timed path reads
+        (`out`, and the buses of voice_poly), as d/<name>.npy in float32.  An array past its share of
+        DUMP_BYTES keeps a fixed sample of its instance columns (the last axis)."""
+        import torch
+        torch.cuda.synchronize(self.dev)
+        os.makedirs(d, exist_ok=True)
+        arrays = {"out": self.out}
+        if self.bus is not None:
+            arrays["bus"] = self.bus
+        share = DUMP_BYTES // self.world // len(arrays)
+        sfx = "" if self.world == 1 else f"_rank{self.rank}"
+        info = {}
+        for name, t in arrays.items():
+            cols = t.shape[-1]
+            keep = min(cols, max(1, share // (t.numel() // cols * 4)))
+            if keep < cols:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cols, keep, replace=False))
+                t = t.index_select(t.dim() - 1, torch.from_numpy(idx).to(self.dev))
+            a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32)
+            np.save(os.path.join(d, f"{name}{sfx}.npy"), a)
+            info[name + sfx] = {"shape": list(a.shape), "columns": f"{keep} of {cols}"}
+        return info
+
     def finish(self) -> dict:
         import torch
 
@@ -616,7 +665,7 @@ class Leg:
         checksum = float(torch.where(finite, out.abs(), torch.zeros_like(out)).sum().item())
         bus_sum = float(bus.abs().sum().item()) if bus is not None else None
         mix_ms = None
-        if bus is not None:            # the mix alone, K launches between one event pair (untimed for value)
+        if bus is not None and args.full:   # the mix alone, K launches between one event pair (untimed for value)
             scratch = torch.zeros_like(bus)
             for _ in range(args.warmup):
                 eng.mix(out, scratch, stream=stream.cuda_stream)
@@ -701,7 +750,7 @@ class Leg:
                 measured.update({"traffic_read": rd, "hbm_read_gbs_measured": rd / (kern_ms * 1e-3) / 1e9,
                                  "frac_read_measured": rd / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS})
         timing = ("median over the repetitions of one HIP event pair around the K timed steps / K, less the mix's "
-                  "own time (one pair around K mix launches after the timed regions)" if bus is not None else
+                  "own time (one pair around K mix launches after the timed regions)" if mix_ms is not None else
                   "median over the repetitions of one HIP event pair on the launch stream around the K timed steps / K "
                   "(launch duration + launch gap)")
         if voice:
@@ -884,9 +933,10 @@ def main():
         for leg in legs[r % m:] + legs[:r % m]:
             leg.warm(W0 if r == 0 else Wr)
             leg.timed(K)
+    dumped = legs[0].dump_outputs(args.dump_outputs) if args.dump_outputs and not args.stub else None
     results = [leg.finish() for leg in legs]
     main_res = results[0]
-    box = _box_copy_rate(torch, dev) if rank == 0 and not args.stub else None
+    box = _box_copy_rate(torch, dev) if rank == 0 and args.full and not args.stub else None
     also_res = {key: res for (_, _, _, key), res in zip(specs[1:], results[1:])}
     cpu_jobs, cpu_reuse, parity_jobs = [], [], []
     if rank == 0 and not args.stub:
@@ -954,6 +1004,8 @@ def main():
             res["mix"] = main_res["mix"]
         if box:
             res["box"] = box
+        if dumped:
+            res["dump_outputs"] = dumped
         full = dict(res, roofline=rf, cpu_baseline=cb, parity=main_res.get("parity"))
         if world == 1 and args.cpu_seconds > 0 and args.workload == "chorus" and not args.stub:
             c1 = cpu_c1(args.sample_rate, args.block)

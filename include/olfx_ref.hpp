@@ -27,7 +27,7 @@
  *                             UpdateHardwareControl, plus the README ChorusEffect setters
  *
  * Compiling the reference's unmodified modules/synthlib/Polyvoice.h and VoiceMap.h against these
- * classes is tested (tests/cpp/test_ref_surface.cpp, recipe in tests/cpp/Makefile).
+ * classes is tested (tests/cpp/test_ref_surface.cpp, recipe in oracle/Makefile).
  *
  * Semantics: one object = one instance of the per-sample pool (include/olfx_sample.h): output is
  * the reference's output one block (olfx_sample_latency, default 256 frames) late; setters, notes,

@@ -2,7 +2,7 @@
  * tests/cpp/test_ref_surface.cpp -- the reference's own types over the GPU (include/olfx_ref.hpp),
  * driven by the reference's own, unmodified headers (TEST INFRASTRUCTURE).
  *
- * Compiled by tests/cpp/Makefile's `test_ref_surface` recipe against
+ * Compiled by oracle/Makefile's `ref_surface` recipe against
  *   /root/reference/modules/corelib/ol_corelib.h, cc_map.h          (ol::core::scale, the CC numbers)
  *   /root/reference/modules/synthlib/Voice.h, SoundSource.h           (the abstract Voice)
  *   /root/reference/modules/synthlib/Polyvoice.h, VoiceMap.h          (the voice containers)

@@ -8,7 +8,7 @@ Chorus / pitch-shift / voice fixtures freeze the build's own spec oracle (parity
 reference implementation exists for them), so they pin the oracle against regressions only.
 
 Inputs are never stored: they are regenerated from xorshift32 seeds.
-Usage:  python tests/golden/gen_golden.py
+Usage:  python tests/golden/gen_golden.py [reference_runs]
 """
 from __future__ import annotations
 
@@ -113,9 +113,35 @@ def fxrack_params(rng: np.random.Generator, n: int) -> np.ndarray:
     return p
 
 
+def reference_runs() -> None:
+    """dattorro_reference_runs.json: the reference build's output, per instance as the fnv1a64 of
+    its bits, for the runs of tests/helpers.py dt_reference_cases (-O2, checked against -O0); and
+    verb_reference_symbols.json: the DattorroVerb_* names the reference build exports."""
+    import re
+    import subprocess
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import dt_reference_cases, lr_hashes, run_dattorro
+    runs = {"generator": "tests/golden/gen_golden.py reference_runs"}
+    for name, (p, x) in dt_reference_cases().items():
+        n = x.shape[2]
+        y = run_dattorro(O.Dattorro(n, ref=True), p, x)
+        y0 = run_dattorro(O.Dattorro(n, ref=True, o0=True), p, x)
+        assert np.array_equal(y.view(np.uint32), y0.view(np.uint32)), "-O0 and -O2 reference builds differ"
+        runs[name] = {"n": n, "frames": x.shape[1], "fnv1a64": lr_hashes(y)}
+    with open(os.path.join(HERE, "dattorro_reference_runs.json"), "w") as f:
+        json.dump(runs, f, indent=1)
+    nm = subprocess.run(["nm", "-D", "--defined-only", O.REF_LIB], capture_output=True, text=True, check=True).stdout
+    names = sorted(s for s in re.findall(r"\bT\s+(\S+)", nm) if "DattorroVerb_" in s)
+    with open(os.path.join(HERE, "verb_reference_symbols.json"), "w") as f:
+        json.dump({"generator": "tests/golden/gen_golden.py reference_runs", "DattorroVerb": names}, f, indent=1)
+    print("wrote dattorro_reference_runs.json, verb_reference_symbols.json")
+
+
 def main() -> None:
     if not O.ref_available() or not O.ref_available(o0=True):
         O.build()
+    if sys.argv[1:] == ["reference_runs"]:       # those two files alone
+        return reference_runs()
     gold: dict = {"generator": "tests/golden/gen_golden.py",
                   "dattorro_reference": "libs/dattorro-verb/verb.cpp via oracle/_ref (g++ -O2 -ffp-contract=off; -O0 cross-check)"}
 
@@ -217,6 +243,7 @@ def main() -> None:
     with open(os.path.join(HERE, "golden.json"), "w") as f:
         json.dump(gold, f, indent=1)
     print("wrote", os.path.join(HERE, "golden.json"))
+    reference_runs()
 
 
 if __name__ == "__main__":

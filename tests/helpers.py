@@ -51,6 +51,39 @@ def dt_params(rng: np.random.Generator, n: int, pre_delay: float) -> np.ndarray:
     return p
 
 
+def dt_reference_cases() -> dict:
+    """The runs in which the restated reverb is compared with the reference build itself
+    (tests/test_oracle.py; recorded by tests/golden/gen_golden.py into
+    tests/golden/dattorro_reference_runs.json): name -> (params [7][n], input [2][frames][n])."""
+    rng = np.random.default_rng(5)
+    n, frames = 16, 70000            # crosses t = 32768 (modulation turn) and the uint16 wrap
+    p = np.empty((7, n), np.float32)
+    p[0] = rng.uniform(0, 1, n)      # per-instance pre-delay is fine on the CPU
+    p[1:] = rng.uniform(0.05, 0.95, (6, n))
+    x = (rng.random((2, frames, n), dtype=np.float32) - 0.5)
+    # extremes of the setters: zero pre-delay, decay clamp both ends, zero/unit gains
+    edge = [[0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+            [1.0, 0.0, 1.0, 1.0, 1.0, 1.0, 1.0],
+            [0.5, 0.5, 0.5, 0.5, 0.5, 0.1, 0.5],
+            [0.99, 0.9, 0.9, 0.9, 0.9, 0.99, 0.01]]
+    return {"random_params": (p, x),
+            "edge_params": (np.asarray(edge, np.float32).T.copy(), noise_block(len(edge), 5000, 99)),
+            "default_params": (None, noise_block(2, 3000, 3))}
+
+
+def run_dattorro(bank, params, x: np.ndarray, threads: int = 1) -> np.ndarray:
+    """Set params [7][n] (None = the defaults) on an oracle reverb bank and process x."""
+    if params is not None:
+        for i in range(params.shape[1]):
+            for f in range(7):
+                bank.set(i, f, float(params[f, i]))
+    return bank.process(x, threads)
+
+
+def lr_hashes(y: np.ndarray) -> list:
+    return [f"{O.fnv1a64_lr(y[0, :, i], y[1, :, i]):016x}" for i in range(y.shape[2])]
+
+
 def chorus_params(rng: np.random.Generator, n: int) -> np.ndarray:
     p = np.empty((8, n), dtype=np.float32)
     p[0] = rng.uniform(0, 3, n)

@@ -53,7 +53,7 @@ def test_gpus_4_end_to_end_with_legs():
     all-reduce per region, rank 0's final line.  The line's value is the job's frames summed over
     the four ranks divided by the median region's time (max over ranks)."""
     n, steps, reps = 4096, 4, 3
-    res = _run_bench("--stub", "--gpus", "4", "--steps", str(steps), "--warmup", "0", "--leg-warmup", "0",
+    res = _run_bench("--stub", "--full", "--gpus", "4", "--steps", str(steps), "--warmup", "0", "--leg-warmup", "0",
                      "--reps", str(reps), "--instances", str(n), "--also", "chain", "--full-json", "", timeout=240)
     assert res["n_gpus"] == 4
     assert res["ranks_reporting"] == 4
@@ -67,3 +67,18 @@ def test_gpus_4_end_to_end_with_legs():
     assert leg["ranks"] == 4 and leg["n"] == 16384
     from ol_dsp_amd.dist import shard
     assert res["output_checksum"] == sum(shard(4 * n, 4, r)[0] for r in range(4))
+
+
+def test_plain_run_is_one_region_of_the_main_workload():
+    """Without --full the line comes from ONE timed region of exactly --steps steps of the main
+    workload: the repetitions and the extra legs are not run even where they are asked for, and no
+    full record is written."""
+    res = _run_bench("--stub", "--steps", "3", "--warmup", "0", "--leg-warmup", "0", "--instances", "64",
+                     "--reps", "4", "--also", "chain")
+    assert res["steps"] == 3 and res["frames"] == 64 * 256 * 3
+    assert res["reps"]["n"] == 1 and len(res["reps"]["kernel_ms"]) == 1
+    assert "also" not in res and "full_json" not in res and "cpu_c1" not in res
+    assert res["cpu_baseline"] is None and res["parity"] is None
+    assert res["higher_is_better"] is True and res["dtype"] == "f32" and res["unit"] == "stereo samples/s"
+    elapsed = res["ms_per_step"] * 3 / 1e3
+    assert abs(res["value"] - res["frames"] / elapsed) <= 1e-6 * res["value"]

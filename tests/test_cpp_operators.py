@@ -50,15 +50,17 @@ def test_cpp_operators_on_gpu():
     assert "17 tests, 0 failures" in r.stdout
 
 
-REF_BIN = os.path.join(CPP, "test_ref_surface")
+ORACLE = os.path.join(os.path.dirname(HERE), "oracle")
+REF_BIN = os.path.join(ORACLE, "_ref", "test_ref_surface")
 REF_HDR = "/root/reference/modules/synthlib/Polyvoice.h"
 
 
 def _build_ref():
-    """tests/cpp/Makefile `test_ref_surface`: include/olfx_ref.hpp under the reference's own,
-    unmodified Polyvoice.h / VoiceMap.h / Voice.h / corelib (built here only; prebuilt on the box)."""
+    """oracle/Makefile `ref_surface`: include/olfx_ref.hpp under the reference's own, unmodified
+    Polyvoice.h / VoiceMap.h / Voice.h / corelib, built into oracle/_ref where the reference is
+    present; elsewhere the prebuilt binary is run."""
     if os.path.exists(REF_HDR):
-        r = subprocess.run(["make", "-s", "-C", CPP, "test_ref_surface"], capture_output=True, text=True, timeout=300)
+        r = subprocess.run(["make", "-s", "-C", ORACLE, "ref_surface"], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stdout + r.stderr
     if not os.path.exists(REF_BIN):
         pytest.skip("test_ref_surface not built (needs /root/reference at build time)")

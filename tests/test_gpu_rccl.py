@@ -57,7 +57,7 @@ def test_reduce_stats_over_rccl_world_1():
 def test_bench_under_a_launcher_world_1():
     """bench.py as one launcher rank (WORLD_SIZE=1 set): the nccl process group of bench.py:main, the
     barriers around the timed region and reduce_stats over RCCL, then the result line."""
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--workload", "chorus", "--instances", "4096",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "1", "--workload", "chorus", "--instances", "4096",
            "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--also", "", "--full-json", ""]
     r = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -13,7 +13,7 @@ for r in $(seq 1 "$runs"); do
     case $lib in *@*) kv=${lib#*@}; lib=${lib%%@*} ;; esac
     [ "$lib" = main ] && lib=ol_dsp_amd/libolfx.so
     for w in $wls; do
-      env "$kv" OLFX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --workload "$w" --also "" --steps 40 --warmup 5 --cpu-seconds 0 \
+      env "$kv" OLFX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --workload "$w" --also "" --steps 40 --warmup 5 --cpu-seconds 0 \
           --no-parity --full-json "" > gpurun_out/ab.log 2>&1 || { tail -n 20 gpurun_out/ab.log; exit 1; }
       python3 - "$w" "$lib $kv" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ for lib in "$@"; do
   [ "$lib" = main ] && lib=ol_dsp_amd/libolfx.so
   for spec in "chain_65536:" "chain_rpd:chain_65536" "dattorro:chain_rpd,chain_65536"; do
     w=${spec%%:*}; also=${spec#*:}
-    OLFX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --workload "$w" --also "$also" --steps 20 --warmup 5 \
+    OLFX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --workload "$w" --also "$also" --steps 20 --warmup 5 \
         --cpu-seconds 0 --no-parity --full-json "" > gpurun_out/ctx.log 2>&1 || { tail -n 20 gpurun_out/ctx.log; exit 1; }
     python - "$lib" "$w" "$also" <<'PY'
 import json, sys

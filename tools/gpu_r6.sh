@@ -66,7 +66,7 @@ for m in "$@"; do
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     b:*)
       w=${m#b:}
-      step "bench_$w" 300 python bench.py --workload "$w" --also "" --steps 20 --warmup 5 --cpu-seconds 0 --full-json "" ;;
+      step "bench_$w" 300 python bench.py --full --workload "$w" --also "" --steps 20 --warmup 5 --cpu-seconds 0 --full-json "" ;;
     p:*)
       w=${m#p:}; wl=$w; [ "$w" = chain_16384 ] && wl=chain
       step "prof_$w" 300 rocprofv3 --kernel-trace --stats -d "$out/prof_$w" -o run --output-format csv -- \
@@ -78,13 +78,13 @@ for m in "$@"; do
     abe:*)
       r=${m#abe:}; w=${r%%:*}; kv=${r#*:}
       for r in 1 2 3; do
-        step "abe_${w}_default_$r" 300 python bench.py --workload "$w" --also "" --steps 50 --warmup 5 \
+        step "abe_${w}_default_$r" 300 python bench.py --full --workload "$w" --also "" --steps 50 --warmup 5 \
             --cpu-seconds 0 --no-parity --full-json ""
-        step "abe_${w}_env_$r" 300 env "$kv" python bench.py --workload "$w" --also "" --steps 50 --warmup 5 --cpu-seconds 0 \
+        step "abe_${w}_env_$r" 300 env "$kv" python bench.py --full --workload "$w" --also "" --steps 50 --warmup 5 --cpu-seconds 0 \
             --no-parity --full-json ""
       done ;;
     bench)
-      step bench_default 900 python bench.py --steps 20 --warmup 5 ;;
+      step bench_default 900 python bench.py --full --steps 20 --warmup 5 ;;
     util:*)
       w=${m#util:}
       step "util_$w" 900 bash tools/pmc_util.sh "$w" 10 ;;
@@ -99,7 +99,7 @@ for m in "$@"; do
     probe)
       step bw_probe 300 tools/bw_probe
       cat "$out/bw_probe.log"
-      step bench_chorus_probe 300 python bench.py --workload chorus --also "" --steps 20 --cpu-seconds 0 --no-parity \
+      step bench_chorus_probe 300 python bench.py --full --workload chorus --also "" --steps 20 --cpu-seconds 0 --no-parity \
           --full-json ""
       cat "$out/bench_chorus_probe.log" ;;
     *) echo "unknown mode $m"; exit 2 ;;
