@@ -31,6 +31,89 @@ def first_mismatch(a: np.ndarray, b: np.ndarray):
     return None if len(d) == 0 else (tuple(d[0]), float(a[tuple(d[0])]), float(b[tuple(d[0])]), len(d))
 
 
+def same_bits_or_nan(a: np.ndarray, b: np.ndarray) -> bool:
+    """The same NaN mask, and the same uint32 bits everywhere else: +-Inf, +-0 and subnormals are
+    compared exactly.  The sign and payload of a NaN are not compared (x86 and the GPU generate
+    different default NaNs): the one relaxation against bits_equal."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    if not np.array_equal(na, nb):
+        return False
+    return np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def first_mismatch_or_nan(a: np.ndarray, b: np.ndarray):
+    """first_mismatch under same_bits_or_nan's rule."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    d = np.argwhere((na != nb) | (~na & ~nb & (a.view(np.uint32) != b.view(np.uint32))))
+    return None if len(d) == 0 else (tuple(d[0]), float(a[tuple(d[0])]), float(b[tuple(d[0])]), len(d))
+
+
+def subnormal_share(y: np.ndarray) -> float:
+    """The share of y's non-zero samples that are subnormal (0 if all are zero)."""
+    a = np.abs(y)
+    sub = (a > 0) & (a < np.finfo(np.float32).tiny)
+    return float(np.count_nonzero(sub) / max(1, np.count_nonzero(y != 0)))
+
+
+def nonfinite_share(y: np.ndarray) -> float:
+    return float(np.mean(~np.isfinite(y)))
+
+
+# ---- signals at the edge of fp32 (tests/test_gpu_edges.py, tests/test_oracle.py) ----
+EDGE_FRAMES = 3072
+EDGE_BLOCKS = [256, 4, 20, 1024, 300, 1468]
+
+
+def poison_table(n: int) -> list:
+    """(channel, frame, instance, value): single non-finite input samples in the first and the last
+    instance and on both sides of a 64-lane wave edge."""
+    t = [(0, 100, 0, np.nan), (1, 7, 5, np.inf), (0, 256, 63, -np.inf), (1, 1000, 64, np.nan),
+         (0, 3, n - 1, np.inf), (1, 3, n - 1, -np.inf)]
+    assert all(i < n for _, _, i, _ in t)
+    return t
+
+
+def poisoned(x: np.ndarray) -> np.ndarray:
+    y = x.copy()
+    for c, f, i, v in poison_table(x.shape[2]):
+        y[c, f, i] = v
+    return y
+
+
+def edge_signals(x: np.ndarray) -> dict:
+    """name -> signal [2][frames][n] built on the noise x: subnormal and loud scalings (exact: powers
+    of two), a burst that decays into exact zeros, signed zero and constants.  All finite."""
+    f = np.float32
+    burst = x.copy()
+    burst[:, 300:] = 0.0
+    alt = np.ones_like(x)
+    alt[:, 1::2] = -1.0
+    return {"subnormal": x * f(2.0 ** -130), "burst": burst, "loud100": x * f(2.0 ** 100),
+            "loud127": x * f(2.0 ** 127), "negzero": np.full_like(x, -0.0), "ones": np.ones_like(x),
+            "alternating": alt}
+
+
+def dt_edge_params(n: int, seed: int = 40) -> np.ndarray:
+    """The reverb's parameters of the edge-signal runs: dt_params with pre-delays in [0, 0.02)."""
+    rng = np.random.default_rng(seed)
+    p = dt_params(rng, n, 0.0)
+    p[0] = rng.uniform(0, 0.02, n)
+    return p
+
+
+def dt_corner_params() -> np.ndarray:
+    """[7][128]: the corners {0, 1}^7 of the reverb's seven setters (pre-delay 0 and 4800 samples,
+    decay at both clamps, gains exactly 0 and 1); bit f of the instance index is field f."""
+    i = np.arange(128)
+    return np.stack([((i >> f) & 1).astype(np.float32) for f in range(7)])
+
+
 def rel_err(a: np.ndarray, ref: np.ndarray) -> float:
     """max |a - ref| / max(|ref|, rms(ref)) per instance (SURVEY 8c acceptance floor)."""
     a = a.astype(np.float64)
@@ -66,9 +149,16 @@ def dt_reference_cases() -> dict:
             [1.0, 0.0, 1.0, 1.0, 1.0, 1.0, 1.0],
             [0.5, 0.5, 0.5, 0.5, 0.5, 0.1, 0.5],
             [0.99, 0.9, 0.9, 0.9, 0.9, 0.99, 0.01]]
-    return {"random_params": (p, x),
+    runs = {"random_params": (p, x),
             "edge_params": (np.asarray(edge, np.float32).T.copy(), noise_block(len(edge), 5000, 99)),
             "default_params": (None, noise_block(2, 3000, 3))}
+    # signals at the edge of fp32 on which the reverb stays finite (edge_signals), 8 instances, and
+    # the 128 corners of the seven setters over the input of the GPU corner run
+    sig = edge_signals(fast_noise(8, EDGE_FRAMES, seed=40))
+    for name in ("subnormal", "loud100", "loud127", "burst", "negzero"):
+        runs["edge_signal_" + name] = (dt_edge_params(8), sig[name])
+    runs["corner_params"] = (dt_corner_params(), fast_noise(128, 4096, seed=4))
+    return runs
 
 
 def run_dattorro(bank, params, x: np.ndarray, threads: int = 1) -> np.ndarray:

@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 import oracle as O
-from helpers import (bits_equal, dt_reference_cases, first_mismatch, fxrack_params, lr_hashes, noise_block, rel_err,
-                     run_dattorro)
+from helpers import (EDGE_FRAMES, bits_equal, dt_edge_params, dt_reference_cases, fast_noise, first_mismatch,
+                     fxrack_params, lr_hashes, noise_block, poison_table, poisoned, rel_err, run_dattorro,
+                     subnormal_share)
 
 
 # ---------------------------------------------------------------- dattorro, vs golden fixtures
@@ -126,6 +127,43 @@ def test_dattorro_reference_O0_equals_O2(reference_runs):
         y2, y0 = O.Dattorro(2, ref=True).process(x), O.Dattorro(2, ref=True, o0=True).process(x)
         assert bits_equal(y2, y0), first_mismatch(y2, y0)
         assert lr_hashes(y0) == recorded
+
+
+@pytest.mark.parametrize("name", ["subnormal", "loud100", "loud127", "burst", "negzero"])
+def test_dattorro_port_equals_reference_edge_signals(reference_runs, name):
+    """Signals at the edge of fp32 (helpers.edge_signals): the reverb stays finite on each, the
+    restatement reproduces the reference's recorded bits, and the subnormal input gives subnormal
+    output (nothing on the CPU side flushes)."""
+    ya = _port_equals_reference(reference_runs["edge_signal_" + name])
+    assert np.all(np.isfinite(ya))
+    if name == "subnormal":
+        assert subnormal_share(ya) >= 0.5
+    if name == "negzero":
+        assert not np.any(ya)
+
+
+def test_dattorro_port_equals_reference_corner_params(reference_runs):
+    """The 128 corners {0, 1}^7 of the seven setters, pre-delay 0 and 4800 samples included."""
+    ya = _port_equals_reference(reference_runs["corner_params"], threads=4)
+    assert np.all(np.isfinite(ya))
+
+
+def test_dattorro_port_equals_reference_poisoned_input():
+    """Single NaN / +-Inf input samples (helpers.poison_table): only the poisoned instances differ
+    from the clean run, and, where oracle/_ref is built, the restatement equals the reference build
+    as arrays, NaN bits included."""
+    n = 70
+    p, x = dt_edge_params(n), fast_noise(n, EDGE_FRAMES, seed=40)
+    xp = poisoned(x)
+    ya = run_dattorro(O.Dattorro(n), p, xp, threads=4)
+    if O.ref_available():
+        yb = run_dattorro(O.Dattorro(n, ref=True), p, xp, threads=4)
+        assert bits_equal(ya, yb), first_mismatch(ya, yb)
+    bad = sorted({i for _, _, i, _ in poison_table(n)})
+    assert all(not np.all(np.isfinite(ya[:, :, i])) for i in bad)
+    clean = np.setdiff1d(np.arange(n), bad)
+    yc = run_dattorro(O.Dattorro(n), p, x, threads=4)
+    assert bits_equal(ya[:, :, clean], yc[:, :, clean])
 
 
 def test_dattorro_empty_block():
