@@ -438,7 +438,7 @@ struct olfx_engine {
     uint32_t *fr_state = nullptr, *fr_coef = nullptr;
     uint32_t n_dt = 0;           // reverb-stage instances: n, or n rounded up to 64 for the chain
     float *dt_rings = nullptr;
-    // standalone reverb: the network (dattorro.hip dattorro_rows) and so its pre-delay ring's layout
+    // standalone reverb: the network (dattorro.hip dattorro_network) and so its pre-delay ring's layout
     float *dt_pre_tmp = nullptr; // a copy of the pre-delay ring while its layout changes
     int dt_net = DT_NET_V4;      // the network of the last block; its pre-delay ring layout: rows unless v4
     bool dt_pre_check = true;    // a pre-delay changed: re-decide the network at the next block
@@ -956,7 +956,7 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
     switch (e->kind) {
     case OLFX_KIND_DATTORRO: {
         if (e->dt_pre_check) {
-            // one pre-delay for all instances or several: the network (dattorro.hip dattorro_rows)
+            // one pre-delay for all instances or several: the network (dattorro.hip dattorro_network)
             // and so the pre-delay ring's layout; its content is converted when that changes
             e->dt_pre_check = false;
             const float *pd = e->params.data() + (size_t)OLFX_DT_PREDELAY * e->n;
@@ -1738,7 +1738,7 @@ double olfx_algorithmic_read_bytes_per_frame(const olfx_engine *e) {
 const char *olfx_kernel_name(const olfx_engine *e) {
     if (!e) return "";
     switch (e->kind) {
-    case OLFX_KIND_DATTORRO:   // the network of the last block (dattorro.hip dattorro_rows)
+    case OLFX_KIND_DATTORRO:   // the network of the last block (dattorro.hip dattorro_network)
         return dattorro_network_name(e->dt_net);
     case OLFX_KIND_CHORUS:
     case OLFX_KIND_PITCHSHIFT: return "chorus_block_v11";

@@ -158,7 +158,35 @@ def dt_reference_cases() -> dict:
     for name in ("subnormal", "loud100", "loud127", "burst", "negzero"):
         runs["edge_signal_" + name] = (dt_edge_params(8), sig[name])
     runs["corner_params"] = (dt_corner_params(), fast_noise(128, 4096, seed=4))
+    # one pre-delay for all instances (the engine's position-major pre-delay tap, dattorro_block_v4):
+    # the delays it serves from registers (0..8), the first from the ring (9), past a 256-frame call
+    # and the setter's maximum; and 70,000 frames at the longest delay the 8,192-slot ring holds
+    for d in UNIFORM_PD:
+        runs[f"uniform_pd_{d}"] = _uniform_pd_run(d, 4, 2048)
+    runs["uniform_long"] = _uniform_pd_run(8191, 8, 70000)
     return runs
+
+
+UNIFORM_PD = (0, 1, 3, 4, 5, 8, 9, 257, 4800)
+UNIFORM_PD_RUNS = [f"uniform_pd_{d}" for d in UNIFORM_PD] + ["uniform_long"]
+
+
+def predelay_value(d) -> np.ndarray:
+    """The float32 setter value(s) of a pre-delay of d samples, built as test_dattorro_predelay_beyond_max
+    builds them (d / 4800 rounded to float32); checked to give d back through uint16(value * 4800.f)."""
+    v = (np.asarray(d, np.float64) / 4800).astype(np.float32)
+    assert np.array_equal((v * np.float32(4800.0)).astype(np.uint16), np.asarray(d)), d
+    return v
+
+
+def _uniform_pd_run(d: int, n: int, frames: int):
+    """Parameters and input drawn as random_params draws them, with their own seed and every
+    instance's pre-delay d samples."""
+    rng = np.random.default_rng([5, d, frames])
+    p = np.empty((7, n), np.float32)
+    p[0] = predelay_value(d)
+    p[1:] = rng.uniform(0.05, 0.95, (6, n))
+    return p, (rng.random((2, frames, n), dtype=np.float32) - 0.5)
 
 
 def run_dattorro(bank, params, x: np.ndarray, threads: int = 1) -> np.ndarray:

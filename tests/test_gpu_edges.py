@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from helpers import (EDGE_BLOCKS, EDGE_FRAMES, bits_equal, chorus_params, dt_corner_params, dt_edge_params,
+from helpers import (EDGE_BLOCKS, EDGE_FRAMES, UNIFORM_PD_RUNS, bits_equal, chorus_params, dt_corner_params, dt_edge_params,
                      dt_reference_cases, edge_signals, fast_noise, first_mismatch, first_mismatch_or_nan,
                      fxrack_params, lr_hashes, nonfinite_share, poison_table, poisoned, same_bits_or_nan,
                      subnormal_share, voice_configs)
@@ -163,12 +163,14 @@ def reference_runs():
 
 @pytest.mark.parametrize("name", ["edge_params", "random_params", "corner_params", "edge_signal_subnormal",
                                   "edge_signal_loud100", "edge_signal_loud127", "edge_signal_burst",
-                                  "edge_signal_negzero"])
+                                  "edge_signal_negzero"] + UNIFORM_PD_RUNS)
 def test_dattorro_equals_reference_hashes(cuda, reference_runs, name):
     """The GPU reverb held to the hashes the REAL reference build produced
     (tests/golden/dattorro_reference_runs.json; tests/test_oracle.py holds the CPU oracle to the
     same): the setter extremes (gains exactly 0 and 1, decay at both clamps), the random run over
-    70,000 frames, the 128 corners, and the all-finite edge signals at n = 8."""
+    70,000 frames, the 128 corners, the all-finite edge signals at n = 8, and the runs with one
+    pre-delay for all instances (dattorro_block_v5 at these sizes; tests/test_gpu_dattorro_v4.py holds
+    dattorro_block_v4 to the same hashes)."""
     p, x, recorded = reference_runs[name]
     n, frames = x.shape[2], x.shape[1]
     e = engine("dattorro", n)

@@ -181,6 +181,41 @@ def test_v5_large_ragged_long_run(cuda):
     e.close()
 
 
+def test_v4_large_ragged_natural_dispatch(cuda):
+    """The twin of test_v5_large_ragged_long_run with one pre-delay for all instances, so the engine
+    itself picks dattorro_block_v4 (no environment switch; tests/test_gpu_dattorro_v4.py forces it at
+    small n): n = CUs x 128 + 37, a partial last wave, a pre-delay of 3 samples (PreTap's register
+    path), calls of 256 frames and of 4 and 1,020 moving t0 off the 16-position rows.  Sampled
+    instances, the partial wave's included, bit-exact against the oracle."""
+    import torch
+    from helpers import dt_params, predelay_value
+    from ol_dsp_amd.workload import noise_torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = cus * 128 + 37
+    p = dt_params(np.random.default_rng(607), n, 0.0)
+    p[0] = predelay_value(3)
+    e = _engine("dattorro", n)
+    e.set_params(0, p)
+    idx = np.unique(np.concatenate([np.arange(12), np.array([63, 64, 127, n // 2]), np.arange(n - 40, n)]))
+    d = O.Dattorro(len(idx))
+    for k, i in enumerate(idx):
+        for f in range(7):
+            d.set(k, f, float(p[f, i]))
+    ys, yrs = [], []
+    for F in [256] * 3 + [4, 1020, 256]:
+        x = torch.cat(noise_torch(len(ys) * 7, n, F, 2, cuda, blocks=1), 1)
+        y = e.process(x)
+        torch.cuda.synchronize()
+        ys.append(y[:, :, idx].cpu().numpy())
+        yrs.append(d.process(np.ascontiguousarray(x[:, :, idx].cpu().numpy())))
+    print(f"\nn={n}: {e.kernel_name}")
+    assert e.kernel_name == "dattorro_block_v4"
+    yg, yr = np.concatenate(ys, 1), np.concatenate(yrs, 1)
+    assert np.all(np.any(yr[:, :512] != 0, axis=(0, 1)))         # no instance compares zeros only
+    assert bits_equal(yg, yr), first_mismatch(yg, yr)
+    e.close()
+
+
 def test_reverb_network_switches_at_full_size(cuda):
     """configs[2]'s 65,536 reverbs: uniform pre-delays run dattorro_block_v4 (pre-delay ring
     position-major), per-instance pre-delays dattorro_block_v5 (ring in rows); each switch converts
@@ -237,6 +272,64 @@ def test_chain_persistent_groups_ragged(cuda):
     yg = y[:, :, idx].cpu().numpy()
     assert bits_equal(yg, yr), first_mismatch(yg, yr)
     e.close()
+
+
+@pytest.mark.parametrize("extra", [70, 72])
+def test_chain_second_group_short_and_odd_chunk_counts(cuda, extra):
+    """chain_block_v5 with two more groups than CUs: workgroups 0 and 1 run a second 64-instance
+    group on the same lanes, its chunk numbers gc = nchunks + c going on through the three LDS
+    buffers (gc % 3), the last group partial (6 or 8 of 64).  Calls of 4, 20, 300, 256, 1,020 and 16
+    frames: 1, 2, 19, 16, 64 and 1 chunks (odd counts, so the second group starts on another buffer
+    than the first), the last chunk short in four of them, its frames past the end left unfilled.
+    n = CUs x 64 + 70 takes per-lane I/O, + 72 cooperative rows.  Sampled instances of the first and
+    second groups of both workgroups bit-exact against the composed oracle.  (The workload's reverb
+    pre-delay is 480 samples, so the output leaves zero only in the 1,020-frame call: what the
+    short calls before it computed is checked through the state they left in the rings.)
+
+    Then the same calls twice more, each with one NaN input sample: instance 5 at frame 2 of the
+    20-frame call; instance CUs x 64 - 1 at the last real frame of the 300-frame call.  The oracle
+    is non-finite on the poisoned instance; every other instance -- CUs x 64 + 5 included, the same
+    workgroup and lane one group later -- has the bits of the clean GPU run, compared on the device
+    over the whole tensors."""
+    import torch
+    from ol_dsp_amd.workload import noise_torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    g1 = cus * 64
+    n = g1 + extra
+    calls = [4, 20, 300, 256, 1020, 16]
+    p = _params("chain", 0, n, clone=False)
+    xs = [torch.cat(noise_torch(k * 7, n, F, 2, cuda, blocks=1), 1) for k, F in enumerate(calls)]
+    torch.cuda.synchronize()
+
+    def run(xs):
+        e = _engine("chain", n)
+        e.set_params(0, p)
+        y = _run(e, xs)
+        e.close()
+        return y
+
+    y = run(xs)
+    assert torch.isfinite(y).all()
+    idx = np.array([0, 5, 63, 64, g1 - 1, g1, g1 + 5, g1 + 63, g1 + 64, n - 1], np.int64)
+    yr = _oracle("chain", p, idx, np.ascontiguousarray(torch.cat(xs, 1)[:, :, idx].cpu().numpy()))
+    yg = y[:, :, idx].cpu().numpy()
+    assert np.all(np.any(yr != 0, axis=(0, 1)))
+    assert bits_equal(yg, yr), first_mismatch(yg, yr)
+    poison = [(1, 2, 5), (2, 299, g1 - 1)]                # (call, frame of the call, instance)
+    for call, frame, inst in poison:
+        xo = torch.cat(xs, 1)[:, :, [inst]].cpu().numpy()
+        xo[0, sum(calls[:call]) + frame, 0] = np.nan
+        yo = _oracle("chain", p, np.array([inst], np.int64), np.ascontiguousarray(xo))
+        assert not np.all(np.isfinite(yo)), f"the oracle stays finite on the poisoned instance {inst}"
+    for call, frame, inst in poison:
+        xp = list(xs)
+        xp[call] = xs[call].clone()
+        xp[call][0, frame, inst] = float("nan")
+        yp = run(xp)
+        assert not torch.isfinite(yp[:, :, inst]).all()
+        yp[:, :, inst] = y[:, :, inst]
+        assert torch.equal(yp.view(torch.int32), y.view(torch.int32)), \
+            f"NaN in instance {inst}: instances {torch.nonzero((yp != y).any(0).any(0)).flatten().tolist()[:16]} differ"
 
 
 @pytest.mark.parametrize("kind", ["voice", "voice_moog"])

@@ -113,8 +113,10 @@ def test_dattorro_predelay_gather_mode_switches(cuda):
     """Per-instance pre-delays switched on and off mid-run (verb.cpp:137-139): uniform -> per
     instance (edges 0..8, 255..257, 4800, past the max) -> uniform -> per instance, calls of 256, 4,
     1028 and 60 frames, bit-exact against the oracle throughout; reset() starts over.  At this size
-    both kinds run dattorro_block_v5 with the pre-delay ring in rows (test_gpu_fullsize.py covers the
-    layout conversions of the large engines, where uniform pre-delays run v4)."""
+    both kinds run dattorro_block_v5 with the pre-delay ring in rows, as does every reverb test of
+    this file and of test_gpu_edges.py below 2 x 64 x CUs instances.  dattorro_block_v4 and the layout
+    conversions between the two: test_gpu_dattorro_v4.py at small ragged n (v4 forced in a child
+    process), test_gpu_fullsize.py at the sizes where uniform pre-delays run v4 by themselves."""
     n = 96
     rng = np.random.default_rng(81)
     p = dt_params(rng, n, 0.2)

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from helpers import (EDGE_FRAMES, bits_equal, dt_edge_params, dt_reference_cases, fast_noise, first_mismatch,
+from helpers import (EDGE_FRAMES, UNIFORM_PD_RUNS, bits_equal, dt_edge_params, dt_reference_cases, fast_noise, first_mismatch,
                      fxrack_params, lr_hashes, noise_block, poison_table, poisoned, rel_err, run_dattorro,
                      subnormal_share)
 
@@ -146,6 +146,16 @@ def test_dattorro_port_equals_reference_corner_params(reference_runs):
     """The 128 corners {0, 1}^7 of the seven setters, pre-delay 0 and 4800 samples included."""
     ya = _port_equals_reference(reference_runs["corner_params"], threads=4)
     assert np.all(np.isfinite(ya))
+
+
+@pytest.mark.parametrize("name", UNIFORM_PD_RUNS)
+def test_dattorro_port_equals_reference_uniform_predelay(reference_runs, name):
+    """One pre-delay for all instances: 0..8 samples (inside the last two 4-frame steps), 9, 257, the
+    setter's maximum 4800, and 8191 over 70,000 frames (the ring's longest delay, across t = 32768
+    and the uint16 wrap) -- the runs the GPU's uniform-pre-delay network is held to as well.  The
+    2,048 frames at 4800 end before the first delayed sample: that run's output is all zeros."""
+    ya = _port_equals_reference(reference_runs[name], threads=4)
+    assert np.all(np.isfinite(ya)) and np.any(ya != 0) == (name != "uniform_pd_4800")
 
 
 def test_dattorro_port_equals_reference_poisoned_input():
