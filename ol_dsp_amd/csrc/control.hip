@@ -2,7 +2,7 @@
 // olfx_control / olfx_update, applied at the next block boundary).
 //
 // The host re-derives the coefficients of the instances whose parameters changed since the last
-// block -- only those, with the reference's setter arithmetic (olfx_engine.cpp derive_*) -- and
+// block -- only those, with the reference's setter arithmetic (olfx_host.cpp derive_*) -- and
 // ships them as one packet with the block (an asynchronous copy on the engine's control stream).
 // This kernel scatters the packet into the field-major coefficient arrays the effect kernels read,
 // on the caller's stream, ahead of the block's launch.  Work and traffic are O(changed instances).

@@ -1,0 +1,800 @@
+// ol_dsp_amd/csrc/olfx_host.cpp -- the HIP-free half of the host side (olfx_host.h): the kind
+// tables, the coefficient derivation (the reference's setter semantics, at control rate), the
+// parameter shadow with its validation, and the control packet's format.
+#include "olfx_host.h"
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+namespace olfx {
+namespace host __attribute__((visibility("hidden"))) {      // as in olfx_host.h: not part of the ABI
+namespace {
+
+uint32_t pow2_at_least(uint32_t x) {
+    uint32_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// a fraction of a cycle in [0, 1] as 64-bit fixed point (2^64 = one cycle); 1.0 wraps to 0
+uint64_t fix64(double cycles) {
+    constexpr double kTwo64 = 18446744073709551616.0;
+    const double v = std::floor(cycles * kTwo64 + 0.5);
+    return v <= 0 ? 0u : (v >= kTwo64 ? (uint64_t)(v - kTwo64) : (uint64_t)v);
+}
+
+uint32_t as_u32(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+
+size_t up4(size_t x) { return (x + 3) & ~(size_t)3; }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Per-kind constants
+// ---------------------------------------------------------------------------------------------
+uint32_t n_params_of(int kind) {
+    switch (kind) {
+    case OLFX_KIND_DATTORRO: return OLFX_DT_NPARAMS;
+    case OLFX_KIND_CHORUS: return OLFX_CH_NPARAMS;
+    case OLFX_KIND_PITCHSHIFT: return OLFX_PS_NPARAMS;
+    case OLFX_KIND_VOICE:
+    case OLFX_KIND_VOICE_MOOG: return OLFX_VC_NPARAMS;
+    case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
+    case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
+    default: return 0;
+    }
+}
+
+uint32_t in_channels(int kind) { return is_voice_kind(kind) ? 0u : 2u; }
+uint32_t out_channels(int kind) { return is_voice_kind(kind) ? 1u : 2u; }
+
+// ol::core::scale (modules/corelib/ol_corelib.h:27-44), t_sample = float
+float core_scale(float in, float inlow, float inhigh, float outlow, float outhigh, float power) {
+    const float denom = inhigh - inlow;
+    const float inscale = denom == 0.f ? 0.f : (float)(1.f / denom);
+    const float outdiff = outhigh - outlow;
+    float value = (in - inlow) * inscale;
+    if (value > 0.0f) value = powf(value, power);
+    else if (value < 0.0f) value = -powf(-value, power);
+    return (value * outdiff) + outlow;
+}
+
+void default_params(int kind, float *p) {
+    switch (kind) {
+    case OLFX_KIND_DATTORRO:
+        // verb.cpp:215-221
+        p[OLFX_DT_PREDELAY] = (float)0.1;
+        p[OLFX_DT_PREFILTER] = (float)0.85;
+        p[OLFX_DT_INPUT_DIFFUSION1] = (float)0.75;
+        p[OLFX_DT_INPUT_DIFFUSION2] = (float)0.625;
+        p[OLFX_DT_DECAY_DIFFUSION] = (float)0.70;
+        p[OLFX_DT_DECAY] = (float)0.75;
+        p[OLFX_DT_DAMPING] = (float)0.95;
+        break;
+    case OLFX_KIND_CHORUS:
+        // mono-chorus.rnbopat param boxes (:431,1772,2226,2660,3420,3854,4353)
+        p[OLFX_CH_PITCH] = 0.0f;
+        p[OLFX_CH_MIX] = 0.5f;
+        p[OLFX_CH_Q] = 0.5f;
+        p[OLFX_CH_CUTOFF] = 0.3f;
+        p[OLFX_CH_PHASE] = 1.0f;
+        p[OLFX_CH_DEPTH] = 0.5f;
+        p[OLFX_CH_RATE] = 0.2f;
+        p[OLFX_CH_WINDOW] = 10.0f;
+        break;
+    case OLFX_KIND_PITCHSHIFT:
+        p[OLFX_PS_SHIFT] = 0.0f;
+        p[OLFX_PS_WINDOW] = 10.0f;
+        break;
+    case OLFX_KIND_VOICE:
+    case OLFX_KIND_VOICE_MOOG:
+        // SynthVoice member defaults (SynthVoice.h:285-311); Config order (Voice.h:14-31)
+        p[OLFX_VC_FILTER_CUTOFF] = 0.0f;
+        p[OLFX_VC_FILTER_RESONANCE] = 0.0f;
+        p[OLFX_VC_FILTER_DRIVE] = 0.0f;
+        p[OLFX_VC_FILTER_ENV_AMOUNT] = 1.0f;
+        p[OLFX_VC_FILTER_ATTACK] = 0.0f;
+        p[OLFX_VC_FILTER_ATTACK_SHAPE] = 1.0f;
+        p[OLFX_VC_FILTER_DECAY] = 0.2f;
+        p[OLFX_VC_FILTER_SUSTAIN] = 0.0f;
+        p[OLFX_VC_FILTER_RELEASE] = 0.0f;
+        p[OLFX_VC_AMP_ENV_AMOUNT] = 0.8f;
+        p[OLFX_VC_AMP_ATTACK] = 0.01f;
+        p[OLFX_VC_AMP_ATTACK_SHAPE] = 1.0f;
+        p[OLFX_VC_AMP_DECAY] = 0.0f;
+        p[OLFX_VC_AMP_SUSTAIN] = 1.0f;
+        p[OLFX_VC_AMP_RELEASE] = 0.01f;
+        p[OLFX_VC_PORTAMENTO] = 0.0f;
+        break;
+    case OLFX_KIND_CHAIN:
+        default_params(OLFX_KIND_CHORUS, p + OLFX_CN_CHORUS0);
+        default_params(OLFX_KIND_PITCHSHIFT, p + OLFX_CN_PITCH0);
+        default_params(OLFX_KIND_DATTORRO, p + OLFX_CN_VERB0);
+        break;
+    case OLFX_KIND_FXRACK:
+        // Fx.h member defaults; DelayFx::Init sets its filter through UpdateMidiControl(CC, 64 / 24)
+        p[OLFX_FR_DELAY_TIME] = 0.5f;
+        p[OLFX_FR_DELAY_FEEDBACK] = 0.5f;
+        p[OLFX_FR_DELAY_BALANCE] = 0.33f;
+        p[OLFX_FR_DELAY_CUTOFF] = core_scale(64.f, 0.f, 127.f, 0.f, 20000.f, 1.f);
+        p[OLFX_FR_DELAY_RESONANCE] = core_scale(24.f, 0.f, 127.f, 0.f, 1.f, 1.f);
+        p[OLFX_FR_REVERB_BALANCE] = 0.1f;
+        p[OLFX_FR_FILTER_CUTOFF] = 20000.f;
+        p[OLFX_FR_FILTER_RESONANCE] = 0.f;
+        p[OLFX_FR_FILTER_DRIVE] = 0.f;
+        p[OLFX_FR_FILTER_TYPE] = 0.f;
+        p[OLFX_FR_MASTER_VOLUME] = 0.8f;
+        p[OLFX_FR_TOPOLOGY] = 0.f;
+        break;
+    default: break;
+    }
+}
+
+void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize) {
+    // pitch ring: delays up to W = 10 ms plus the interpolation neighbour
+    *psize = pow2_at_least((uint32_t)std::ceil(10.0 * sr / 1000.0) + 2);
+    // chorus ring: delays up to 2 D, D <= 12 ms (delay~ @maxsize samplerate*2 is never reached)
+    *csize = pow2_at_least(2u * (uint32_t)std::ceil(12.0 * sr / 1000.0) + 2);
+}
+
+uint64_t state_bytes(int kind, uint32_t n, float sr) {
+    uint32_t ps, cs;
+    chorus_sizes(sr, &ps, &cs);
+    const uint64_t dt = (uint64_t)dt_total_floats() * 4 + DTS_N * 4 + DTC_N * 4;
+    const uint64_t ch = (uint64_t)2 * (ps + cs) * 4 + CHS_N * 4 + CHC_N * 4;
+    const uint64_t vc = (uint64_t)VCS_N * 4 + VCC_N * 4;
+    switch (kind) {
+    case OLFX_KIND_DATTORRO: return dt * n;
+    case OLFX_KIND_CHORUS:
+    case OLFX_KIND_PITCHSHIFT: return ch * n;
+    case OLFX_KIND_VOICE: return vc * n;
+    case OLFX_KIND_VOICE_MOOG: return vc * n + (uint64_t)(VCS_N_MOOG - VCS_N) * 4 * n;
+    case OLFX_KIND_CHAIN: return (dt + 2 * ch) * n;
+    case OLFX_KIND_FXRACK: return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n;
+    default: return 0;
+    }
+}
+
+double algorithmic_bytes_per_frame(int kind) {
+    // DESIGN.md section 4 / SURVEY.md section 8d, B = 256: compulsory ring traffic + I/O
+    switch (kind) {
+    case OLFX_KIND_DATTORRO: return 164.6;     // 148.6 state + 8 in + 8 out (stereo in)
+    case OLFX_KIND_CHORUS: return 56.0;        // 2 x (pitch w + 2 taps + chorus w + tap) x 4 + 16 I/O
+    case OLFX_KIND_PITCHSHIFT: return 40.0;    // 2 x (w + 2 taps) x 4 + 16 I/O
+    case OLFX_KIND_VOICE: return 5.4;          // 4 B out + per-block state
+    case OLFX_KIND_VOICE_MOOG: return 5.7;     // 4 B out + per-block state (9 more state words)
+    case OLFX_KIND_CHAIN: return 228.6;
+    case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
+    default: return 0.0;
+    }
+}
+
+double algorithmic_read_bytes_per_frame(int kind) {
+    // the read share of the figures above (the north star's "HBM-read roofline"): every tap read
+    // of data older than the block, counted once, plus the input
+    switch (kind) {
+    case OLFX_KIND_DATTORRO: return 6445.0 * 4.0 / 256.0 + 8.0;   // 27 taps: sum min(d, 256) = 6,445 floats; + 8 in
+    case OLFX_KIND_CHORUS: return 32.0;        // 2 x (2 pitch taps + chorus tap) x 4 + 8 in
+    case OLFX_KIND_PITCHSHIFT: return 24.0;    // 2 x 2 taps x 4 + 8 in
+    case OLFX_KIND_VOICE: return 0.7;          // per-block state and coefficients
+    case OLFX_KIND_VOICE_MOOG: return 0.85;
+    case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
+    case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
+    default: return 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Coefficient derivation (control rate, host).  These restate the reference setters.
+// ---------------------------------------------------------------------------------------------
+uint32_t dattorro_predelay_samples(float v) {
+    // verb.cpp:137-139: uint16(value * 4800.f) into DelayBuffer_setDelay, whose read offset
+    // mask + 1 - delay (verb.cpp:59-61) on the 8192-sample pre-delay ring makes the effective delay
+    // uint16(value * 4800) mod 8192 (olfx_set_params accepts value * 4800 in [0, 65536))
+    float d = v * 4800.0f;
+    return d <= 0.0f ? 0u : ((uint32_t)(uint16_t)d & (kDtSize[DT_PRE] - 1u));
+}
+
+void derive_dattorro(const float *p, float *c) {
+    c[DTC_PREFILTER] = p[OLFX_DT_PREFILTER];
+    c[DTC_IN1] = p[OLFX_DT_INPUT_DIFFUSION1];
+    c[DTC_IN2] = p[OLFX_DT_INPUT_DIFFUSION2];
+    c[DTC_DD1] = p[OLFX_DT_DECAY_DIFFUSION];
+    c[DTC_DAMPING] = p[OLFX_DT_DAMPING];
+    c[DTC_DECAY] = p[OLFX_DT_DECAY];
+    // verb.cpp:49,162-165: clamp(t_sample x, ...) narrows value+0.15 to float
+    float x = (float)((double)p[OLFX_DT_DECAY] + 0.15);
+    c[DTC_DD2] = x < 0.25f ? 0.25f : (x > 0.5f ? 0.5f : x);
+    c[DTC_PREDELAY] = (float)dattorro_predelay_samples(p[OLFX_DT_PREDELAY]);
+}
+
+// chorus: p = [OLFX_CH_*], c = [CHC_*] (u32 words)
+void derive_chorus(const float *p, double sr, uint32_t *c) {
+    const double pitch = clampf(p[OLFX_CH_PITCH], 0.0f, 3.0f);
+    const double mix = clampf(p[OLFX_CH_MIX], 0.0f, 1.0f);
+    const double q = clampf(p[OLFX_CH_Q], 0.0f, 1.0f);
+    const double cutoff = clampf(p[OLFX_CH_CUTOFF], 0.0f, 1.0f);
+    const double phase = clampf(p[OLFX_CH_PHASE], 0.0f, 1.0f);
+    const double depth = clampf(p[OLFX_CH_DEPTH], 0.08f, 1.0f);
+    const double rate = clampf(p[OLFX_CH_RATE], 0.01f, 1.0f);
+    const double window = clampf(p[OLFX_CH_WINDOW], 4.0f, 10.0f);
+
+    const double rate_hz = 0.01 + rate * (0.5 - 0.01);           // scale 0 1 0.01 0.5 (:3935)
+    const double depth_ms = 1.0 + depth * (12.0 - 1.0);          // scale 0 1 1 12 1   (:3436)
+    const double fc = 300.0 + cutoff * (15000.0 - 300.0);         // scale 0 1 300 15000 1 (:2242)
+    // 64-bit phasors: the increment rounding drifts a phase by < 2^-64 cycle per sample
+    const uint64_t lfo_inc = fix64(rate_hz / sr), lfo_off = fix64(phase), ps_inc = fix64(pitch / sr);
+    c[CHC_LFO_INC] = (uint32_t)(lfo_inc >> 32);
+    c[CHC_LFO_INC_LO] = (uint32_t)lfo_inc;
+    c[CHC_LFO_OFF] = (uint32_t)(lfo_off >> 32);                   // phase 1.0 wraps to 0
+    c[CHC_LFO_OFF_LO] = (uint32_t)lfo_off;
+    c[CHC_PS_INC] = (uint32_t)(ps_inc >> 32);
+    c[CHC_PS_INC_LO] = (uint32_t)ps_inc;
+    // D = mstosamps (:3897) as a double; W = mstosamps(window) in 32.32 fixed point (spec v2,
+    // olfx_internal.h pitch_split / chorus_split)
+    const double D = depth_ms * sr / 1000.0;
+    uint64_t Dbits;
+    std::memcpy(&Dbits, &D, 8);
+    c[CHC_DEPTH] = (uint32_t)(Dbits >> 32);
+    c[CHC_DEPTH_LO] = (uint32_t)Dbits;
+    const uint64_t Wfix = (uint64_t)std::floor(window * sr / 1000.0 * 4294967296.0 + 0.5);
+    c[CHC_WINDOW] = (uint32_t)(Wfix >> 32);
+    c[CHC_WINDOW_LO] = (uint32_t)Wfix;
+    // lores~ -> RBJ biquad low-pass, Q = 1/sqrt(2) + 20 q^3 (declared)
+    const double Q = 0.70710678118654752 + 20.0 * q * q * q;
+    const double w0 = 2.0 * 3.14159265358979323846 * fc / sr;
+    const double cw = std::cos(w0), sw = std::sin(w0);
+    const double alpha = sw / (2.0 * Q);
+    const double a0 = 1.0 + alpha;
+    c[CHC_B0] = as_u32((float)((1.0 - cw) * 0.5 / a0));
+    c[CHC_B1] = as_u32((float)((1.0 - cw) / a0));
+    c[CHC_B2] = as_u32((float)((1.0 - cw) * 0.5 / a0));
+    c[CHC_A1] = as_u32((float)(-2.0 * cw / a0));
+    c[CHC_A2] = as_u32((float)((1.0 - alpha) / a0));
+    const float mixf = (float)mix;
+    c[CHC_MIX] = as_u32(mixf);
+    c[CHC_DRY] = as_u32(1.0f - mixf);                             // !- 1 (:1176)
+}
+
+// pitch-shift stage only: reuse the chorus coefficient block (mode 1 ignores the rest)
+void derive_pitchshift(const float *p, double sr, uint32_t *c) {
+    float cp[OLFX_CH_NPARAMS];
+    default_params(OLFX_KIND_CHORUS, cp);
+    cp[OLFX_CH_PITCH] = p[OLFX_PS_SHIFT];
+    cp[OLFX_CH_WINDOW] = p[OLFX_PS_WINDOW];
+    derive_chorus(cp, sr, c);
+}
+
+namespace {
+
+// DaisySP Adsr coefficient setters (restated; DaisySP is absent from the reference tree, see
+// DESIGN.md "parity unpinned"): SetAttackTime / SetTimeConstant.
+float adsr_attack_d0(float T, float shape, float sr, float *target_out) {
+    float target = 9.f * powf(shape, 10.f) + 0.3f * shape + 1.01f;
+    *target_out = target;
+    if (T > 0.f) {
+        float logTarget = logf(1.f - (1.f / target));
+        return 1.f - expf(logTarget / (T * sr));
+    }
+    return 1.f;
+}
+float adsr_time_d0(float T, float sr) {
+    if (T > 0.f) {
+        const float target = logf((float)(1. / M_E));
+        return 1.f - expf(target / (T * sr));
+    }
+    return 1.f;
+}
+float adsr_sustain(float s) { return (s <= 0.f) ? -0.01f : (s > 1.f ? 1.f : s); }
+
+// FxRack<2> (modules/fxlib/Fx.h:398-492): DelayLine::SetDelay(scale(time, 0,1, 0,48000, 1)),
+// and FilterFx::Update = Svf SetFreq, SetRes, SetDrive (DaisySP restated, as oracle/fxrack_ref.c)
+void svf_coef(float cutoff, float res_in, float drive_in, float sr, float *freq, float *damp, float *drive) {
+    const float fc = clampf(cutoff, 1.0e-6f, sr / 3.f);
+    const float f = 2.0f * sinf(3.1415927410125732f * std::min(0.25f, fc / (sr * 2.0f)));
+    const float res = clampf(res_in, 0.f, 1.f);
+    *freq = f;
+    *damp = std::min(2.0f * (1.0f - powf(res, 0.25f)), std::min(2.0f, 2.0f / f - f * 0.5f));
+    *drive = clampf(drive_in * 0.1f, 0.f, 1.f) * res;
+}
+
+}  // namespace
+
+void derive_fxrack(const float *p, float sr, uint32_t *c) {
+    auto put = [&](int k, float v) { std::memcpy(&c[k], &v, 4); };
+    const float dly = core_scale(p[OLFX_FR_DELAY_TIME], 0.f, 1.f, 0.f, (float)kFrMaxDelay, 1.f);
+    const int32_t id = (int32_t)dly;
+    c[FRC_DELAY] = (uint32_t)id < kFrMaxDelay ? (uint32_t)id : kFrMaxDelay - 1;
+    put(FRC_FRAC, dly - (float)id);
+    put(FRC_FEEDBACK, p[OLFX_FR_DELAY_FEEDBACK]);
+    put(FRC_DBAL, p[OLFX_FR_DELAY_BALANCE]);
+    float f, d, dr;
+    svf_coef(p[OLFX_FR_DELAY_CUTOFF], p[OLFX_FR_DELAY_RESONANCE], 0.f, sr, &f, &d, &dr);
+    put(FRC_DFREQ, f); put(FRC_DDAMP, d); put(FRC_DDRIVE, dr);
+    put(FRC_RBAL, p[OLFX_FR_REVERB_BALANCE]);
+    svf_coef(p[OLFX_FR_FILTER_CUTOFF], p[OLFX_FR_FILTER_RESONANCE], p[OLFX_FR_FILTER_DRIVE], sr, &f, &d, &dr);
+    put(FRC_FFREQ, f); put(FRC_FDAMP, d); put(FRC_FDRIVE, dr);
+    c[FRC_FTYPE] = (uint32_t)(int32_t)p[OLFX_FR_FILTER_TYPE];
+    const uint32_t topo = (uint32_t)p[OLFX_FR_TOPOLOGY];     // 0..4 (validated by olfx_set_params)
+    c[FRC_TOPO] = topo;
+    put(FRC_MASTER, topo ? 1.0f : p[OLFX_FR_MASTER_VOLUME]);   // x 1.0f is exact: no FxRack, no master
+}
+
+// Voice: `configured` = false reproduces SynthVoice::Init without any Update()
+// (SynthVoice.h:31-39): DaisySP Init defaults in the envelopes and the Svf.
+void derive_voice(const float *p, bool configured, bool moog, float sr, float *c) {
+    float tgt;
+    if (!configured) {
+        // daisysp::Adsr::Init: attack 0.1 s shape 0, decay 0.1 s, release 0.1 s, sustain 0.7
+        c[VCC_ATK_D0A] = adsr_attack_d0(0.1f, 0.0f, sr, &tgt); c[VCC_ATK_TGT_A] = tgt;
+        c[VCC_DEC_D0A] = adsr_time_d0(0.1f, sr);
+        c[VCC_REL_D0A] = adsr_time_d0(0.1f, sr);
+        c[VCC_SUS_A] = 0.7f;
+        c[VCC_ATK_D0F] = c[VCC_ATK_D0A]; c[VCC_ATK_TGT_F] = tgt;
+        c[VCC_DEC_D0F] = c[VCC_DEC_D0A];
+        c[VCC_REL_D0F] = c[VCC_REL_D0A];
+        c[VCC_SUS_F] = 0.7f;
+        // daisysp::Svf::Init: res 0.5, drive 0.5
+        c[VCC_DAMP_RES] = 2.0f * (1.0f - powf(0.5f, 0.25f));
+        c[VCC_DRIVE] = 0.5f;
+    } else {
+        c[VCC_ATK_D0A] = adsr_attack_d0(p[OLFX_VC_AMP_ATTACK], p[OLFX_VC_AMP_ATTACK_SHAPE], sr, &tgt);
+        c[VCC_ATK_TGT_A] = tgt;
+        c[VCC_DEC_D0A] = adsr_time_d0(p[OLFX_VC_AMP_DECAY], sr);
+        c[VCC_REL_D0A] = adsr_time_d0(p[OLFX_VC_AMP_RELEASE], sr);
+        c[VCC_SUS_A] = adsr_sustain(p[OLFX_VC_AMP_SUSTAIN]);
+        c[VCC_ATK_D0F] = adsr_attack_d0(p[OLFX_VC_FILTER_ATTACK], p[OLFX_VC_FILTER_ATTACK_SHAPE], sr, &tgt);
+        c[VCC_ATK_TGT_F] = tgt;
+        c[VCC_DEC_D0F] = adsr_time_d0(p[OLFX_VC_FILTER_DECAY], sr);
+        c[VCC_REL_D0F] = adsr_time_d0(p[OLFX_VC_FILTER_RELEASE], sr);
+        c[VCC_SUS_F] = adsr_sustain(p[OLFX_VC_FILTER_SUSTAIN]);
+        // Svf::SetRes then Svf::SetDrive (SynthVoice::Update, SynthVoice.h:82-83)
+        float res = fminf(fmaxf(p[OLFX_VC_FILTER_RESONANCE], 0.f), 1.f);
+        float pre_drive = fminf(fmaxf(p[OLFX_VC_FILTER_DRIVE] * 0.1f, 0.f), 1.f);
+        c[VCC_DAMP_RES] = 2.0f * (1.0f - powf(res, 0.25f));
+        c[VCC_DRIVE] = pre_drive * res;
+    }
+    c[VCC_AMP_AMT] = p[OLFX_VC_AMP_ENV_AMOUNT];
+    c[VCC_CUTOFF] = p[OLFX_VC_FILTER_CUTOFF];
+    c[VCC_FENV_AMT] = p[OLFX_VC_FILTER_ENV_AMOUNT];
+    // daisysp::Port (in-tree stub, Portamento.h:223-226): SynthVoice::Init passes the member
+    // portamento_htime (SynthVoice.h:37), Update SetHtime(portamento_htime): either way the member
+    float htime = p[OLFX_VC_PORTAMENTO];
+    c[VCC_PORT_COEF] = expf(-1.0f / (htime * sr));
+    c[VCC_FC_MAX] = sr / 3.f;
+    c[VCC_SR] = sr;
+    c[VCC_INV_SR] = 1.0f / sr;
+    if (moog) {
+        // daisysp::LadderFilter: Init -> SetRes(0.2), SetInputDrive(0.5) (drive <= 1: drive_scaled =
+        // drive), sr_int_recip_ = 1 / (sr * 4); Update -> MoogFilter::SetRes -> SetRes(res):
+        // K = 4 * clamp(res, 0, kMaxResonance 1.8); MoogFilter::SetDrive is a no-op
+        const float res = configured ? p[OLFX_VC_FILTER_RESONANCE] : 0.2f;
+        c[VCC_LADDER_K] = 4.0f * fminf(fmaxf(res, 0.0f), 1.8f);
+        c[VCC_LADDER_DRIVE] = 0.5f;
+        c[VCC_LADDER_WREC] = 1.0f / (sr * 4);
+    }
+}
+
+Segments coef_segments(int kind) {
+    switch (kind) {
+    case OLFX_KIND_DATTORRO: return {1, {DTC_N, 0, 0}};
+    case OLFX_KIND_CHORUS:
+    case OLFX_KIND_PITCHSHIFT: return {1, {CHC_N, 0, 0}};
+    case OLFX_KIND_CHAIN: return {3, {CHC_N, CHC_N, DTC_N}};       // chorus, pitch-shift, reverb
+    case OLFX_KIND_FXRACK: return {1, {FRC_N, 0, 0}};
+    case OLFX_KIND_VOICE:
+    case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
+    default: return {0, {0, 0, 0}};
+    }
+}
+
+void Shadow::derive_record(uint32_t i, uint32_t *w) const {
+    float p[OLFX_CN_NPARAMS > OLFX_VC_NPARAMS ? OLFX_CN_NPARAMS : OLFX_VC_NPARAMS];
+    for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
+    static_assert((int)VCC_N >= (int)DTC_N, "fc holds either kind's float coefficients");
+    float fc[VCC_N];
+    switch (kind) {
+    case OLFX_KIND_DATTORRO:
+        derive_dattorro(p, fc);
+        std::memcpy(w, fc, DTC_N * 4);
+        break;
+    case OLFX_KIND_CHORUS: derive_chorus(p, sr, w); break;
+    case OLFX_KIND_PITCHSHIFT: derive_pitchshift(p, sr, w); break;
+    case OLFX_KIND_CHAIN:
+        derive_chorus(p + OLFX_CN_CHORUS0, sr, w);
+        derive_pitchshift(p + OLFX_CN_PITCH0, sr, w + CHC_N);
+        derive_dattorro(p + OLFX_CN_VERB0, fc);
+        std::memcpy(w + 2 * CHC_N, fc, DTC_N * 4);
+        break;
+    case OLFX_KIND_FXRACK: derive_fxrack(p, sr, w); break;
+    case OLFX_KIND_VOICE:
+    case OLFX_KIND_VOICE_MOOG:
+        derive_voice(p, configured[i] != 0, kind == OLFX_KIND_VOICE_MOOG, sr, fc);
+        std::memcpy(w, fc, VCC_N * 4);
+        break;
+    default: break;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The parameter shadow: validation and bookkeeping
+// ---------------------------------------------------------------------------------------------
+int Shadow::fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+void Shadow::reset() {
+    params.assign((size_t)n_params * n, 0.f);
+    float d[OLFX_CN_NPARAMS > OLFX_VC_NPARAMS ? OLFX_CN_NPARAMS : OLFX_VC_NPARAMS];
+    default_params(kind, d);
+    for (uint32_t f = 0; f < n_params; ++f)
+        std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
+    configured.assign(n, 0);
+    n_components = 0;
+    pre_changed = true;
+    events.clear();
+    ev_slot.assign(n, -1);
+    dirty_list.clear();
+    dirty_mark.assign(n, 0);
+    mark_dirty(0, n);                        // every coefficient is derived at the first block
+}
+
+void Shadow::mark_dirty(uint32_t first, uint32_t count) {
+    for (uint32_t k = first; k < first + count; ++k)
+        if (!dirty_mark[k]) {
+            dirty_mark[k] = 1;
+            dirty_list.push_back(k);
+        }
+}
+
+// A parameter value the reference's setter gives a meaning to (nullptr) or why not.
+const char *Shadow::bad_value(uint32_t field, float v) const {
+    if (!std::isfinite(v)) return "non-finite value";
+    // the reference converts value * MAX_PREDELAY (4800) to uint16 (verb.cpp:137-139): values whose
+    // product leaves [0, 65536) have no defined meaning there
+    const bool predelay = (kind == OLFX_KIND_DATTORRO && field == OLFX_DT_PREDELAY) ||
+                          (kind == OLFX_KIND_CHAIN && field == OLFX_CN_VERB0 + OLFX_DT_PREDELAY);
+    if (predelay && !(v >= 0.f && v * 4800.0f < 65536.0f)) return "pre-delay outside [0, 65536/4800)";
+    if (kind == OLFX_KIND_FXRACK && field == OLFX_FR_TOPOLOGY && !(v >= 0.f && v <= 4.f && v == (float)(int)v))
+        return "rack topology must be 0, 1, 2, 3 or 4";
+    return nullptr;
+}
+
+// One parameter of one instance; the rack's count of standalone components (topology >= 2, the
+// kernel variant that serves them) follows its topology field.
+void Shadow::store_param(uint32_t field, uint32_t inst, float v) {
+    float &slot = params[(size_t)field * n + inst];
+    if (kind == OLFX_KIND_DATTORRO && field == OLFX_DT_PREDELAY) pre_changed = true;
+    if (kind == OLFX_KIND_FXRACK && field == OLFX_FR_TOPOLOGY)
+        n_components += (v >= 2.f ? 1 : 0) - (slot >= 2.f ? 1 : 0);
+    slot = v;
+}
+
+int Shadow::set_range(uint32_t first, uint32_t count, uint32_t field0, uint32_t n_fields, const float *values) {
+    if (!values || (uint64_t)first + count > n || (uint64_t)field0 + n_fields > n_params)
+        return fail(OLFX_E_ARG, "olfx_set_params: range out of bounds");
+    // validate everything first: a rejected call changes nothing
+    for (uint32_t f = 0; f < n_fields; ++f)
+        for (uint32_t k = 0; k < count; ++k)
+            if (const char *why = bad_value(field0 + f, values[(size_t)f * count + k]))
+                return fail(OLFX_E_ARG, "olfx_set_params: %s", why);
+    for (uint32_t f = 0; f < n_fields; ++f)
+        for (uint32_t k = 0; k < count; ++k) store_param(field0 + f, first + k, values[(size_t)f * count + k]);
+    if (is_voice_kind(kind))
+        for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
+    mark_dirty(first, count);
+    return OLFX_OK;
+}
+
+int Shadow::set_list(uint32_t field, const uint32_t *inst, const float *values, uint32_t count) {
+    if (count && (!inst || !values)) return fail(OLFX_E_ARG, "olfx_set_param_list: null list");
+    if (field >= n_params) return fail(OLFX_E_ARG, "olfx_set_param_list: field out of range");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (inst[k] >= n) return fail(OLFX_E_ARG, "olfx_set_param_list: instance %u out of range", inst[k]);
+        if (const char *why = bad_value(field, values[k])) return fail(OLFX_E_ARG, "olfx_set_param_list: %s", why);
+    }
+    for (uint32_t k = 0; k < count; ++k) {
+        store_param(field, inst[k], values[k]);
+        if (is_voice_kind(kind)) configured[inst[k]] = 1;
+        mark_dirty(inst[k], 1);
+    }
+    return OLFX_OK;
+}
+
+int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
+    if (!is_voice_kind(kind)) return set_range(inst, 1, field, 1, &value);
+    if (inst >= n || field >= n_params) return fail(OLFX_E_ARG, "olfx_set_member: out of range");
+    if (const char *why = bad_value(field, value)) return fail(OLFX_E_ARG, "olfx_set_member: %s", why);
+    // SynthVoice::Process reads filter_cutoff, filter_env_amount and amp_env_amount itself every
+    // sample (SynthVoice.h:42-52): writing them takes effect at once, Update()d or not.  Re-deriving
+    // at the next block changes nothing else, since every other member still holds the value the
+    // last Update() saw (they change only through olfx_set_params, i.e. with an Update()).
+    const bool process_reads = field == OLFX_VC_FILTER_CUTOFF || field == OLFX_VC_FILTER_ENV_AMOUNT ||
+                               field == OLFX_VC_AMP_ENV_AMOUNT;
+    // the other members feed the components only through Update() (SynthVoice.h:66-98); written
+    // after the first Update() they would take effect at the next block as if Update() had run,
+    // which SynthVoice does not do: refused instead of silently diverging
+    if (configured[inst] && !process_reads)
+        return fail(OLFX_E_STATE, "olfx_set_member: instance %u is already Update()d (use olfx_set_params)", inst);
+    store_param(field, inst, value);                    // no Update(): `configured` unchanged
+    mark_dirty(inst, 1);
+    return OLFX_OK;
+}
+
+int Shadow::update(uint32_t first, uint32_t count) {
+    if ((uint64_t)first + count > n) return fail(OLFX_E_ARG, "olfx_update: range out of bounds");
+    if (is_voice_kind(kind))
+        for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
+    mark_dirty(first, count);
+    return OLFX_OK;
+}
+
+bool Shadow::uniform_predelay() const {
+    const float *pd = params.data() + (size_t)OLFX_DT_PREDELAY * n;
+    const uint32_t d0 = dattorro_predelay_samples(pd[0]);
+    for (uint32_t i = 1; i < n; ++i)
+        if (dattorro_predelay_samples(pd[i]) != d0) return false;
+    return true;
+}
+
+// ---- control changes (corelib/cc_map.h) ----
+namespace {
+enum : uint8_t {
+    CC_CTL_PORTAMENTO = 5, CC_CTL_VOLUME = 7,
+    CC_REVERB_BALANCE = 34,
+    CC_DELAY_TIME = 35, CC_DELAY_FEEDBACK = 36, CC_DELAY_CUTOFF = 37, CC_DELAY_RESONANCE = 38,
+    CC_DELAY_BALANCE = 39,
+    CC_FILTER_CUTOFF = 41, CC_FILTER_RESONANCE = 42, CC_FILTER_DRIVE = 44,
+    CC_FX_FILTER_CUTOFF = 45, CC_FX_FILTER_RESONANCE = 46, CC_FX_FILTER_TYPE = 47, CC_FX_FILTER_DRIVE = 48,
+    CC_ENV_FILT_AMT = 73, CC_ENV_FILT_A = 74, CC_ENV_FILT_D = 75, CC_ENV_FILT_S = 76, CC_ENV_FILT_R = 77,
+    CC_ENV_AMP_A = 108, CC_ENV_AMP_D = 109, CC_ENV_AMP_S = 110, CC_ENV_AMP_R = 111,
+    CC_OSC_1_VOLUME = 114,
+};
+}  // namespace
+
+int Shadow::control(const olfx_control_event *ev, uint32_t count) {
+    if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
+        uint32_t field;
+        float v;
+        uint8_t control = ev[k].control;
+        const float topo = kind == OLFX_KIND_FXRACK ? params[(size_t)OLFX_FR_TOPOLOGY * n + ev[k].inst] : 0.f;
+        if (topo != 0.f) {
+            // No FxRack around these instances (ol_daisy/app/synth/main.cpp:201-207 sends every CC to
+            // delay_fx, reverb_fx and filter_fx directly): CC_FILTER_* (41-44) reach a FilterFx's own
+            // handler (Fx.h:116-139), which the rack field map reaches as CC_FX_FILTER_* (45-48);
+            // FxRack's own CC_FX_FILTER_* and master volume (CC 7) reach nothing.  A component alone
+            // takes only its own controls: DelayFx 35-39 (Fx.h:218-267), ReverbFx the reverb CCs (of
+            // which only the balance, 34, is audible through the ReverbSc stub), FilterFx 41-44.
+            const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
+            const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
+            const bool takes = topo == 1.f ? (filter_cc || delay_cc || control == CC_REVERB_BALANCE)
+                             : topo == 2.f ? delay_cc : topo == 3.f ? control == CC_REVERB_BALANCE : filter_cc;
+            if (!takes) continue;
+            if (filter_cc) control = (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF);
+        }
+        const int rc = olfx_control_map(kind, control, ev[k].source, ev[k].value, &field, &v);
+        if (rc == OLFX_IGNORED) continue;
+        if (rc != OLFX_OK) return fail(rc, "olfx_control: event %u", k);
+        if (field == OLFX_FIELD_UPDATE_ONLY) {    // Update() with unchanged members
+            if (is_voice_kind(kind)) configured[ev[k].inst] = 1;
+            mark_dirty(ev[k].inst, 1);
+            continue;
+        }
+        if (const int r2 = set_range(ev[k].inst, 1, field, 1, &v)) return r2;
+    }
+    return OLFX_OK;
+}
+
+int Shadow::note_events(const olfx_event *ev, uint32_t count) {
+    if (!is_voice_kind(kind)) return fail(OLFX_E_STATE, "olfx_note_events: not a voice engine");
+    if (count && !ev) return fail(OLFX_E_ARG, "olfx_note_events: null events");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_GATE_OFF)
+            return fail(OLFX_E_ARG, "olfx_note_events: bad event %u", k);
+    }
+    for (uint32_t k = 0; k < count; ++k)
+        events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
+    return OLFX_OK;
+}
+
+int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
+    if (!is_voice_kind(kind)) return fail(OLFX_E_STATE, "olfx_voice_events: not a voice engine");
+    if (count && !ev) return fail(OLFX_E_ARG, "olfx_voice_events: null events");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_SET_FREQUENCY ||
+            (ev[k].type == OLFX_EV_SET_FREQUENCY && !std::isfinite(ev[k].value)))
+            return fail(OLFX_E_ARG, "olfx_voice_events: bad event %u", k);
+    }
+    events.insert(events.end(), ev, ev + count);
+    return OLFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The control packet (parameters and note events at the block boundary; JUCE-host pattern,
+// modules/juce/host/host.cpp:646-653)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// daisysp::mtof of a MIDI note, from a table of the same expression (notes are 0..127; one powf
+// per NoteOn had been the largest host cost of a block with note events)
+float mtof_note(uint8_t note) {
+    static const std::array<float, 128> t = [] {
+        std::array<float, 128> r{};
+        for (int k = 0; k < 128; ++k) r[(size_t)k] = powf(2.f, ((float)k - 69.0f) / 12.0f) * 440.0f;
+        return r;
+    }();
+    return t[note & 127u];
+}
+}  // namespace
+
+// The block's note events, one record per voice, in order of first appearance (VEV_*,
+// olfx_layout.h).  Calls on one voice compose field by field, as their in-order application does
+// (SynthVoice.h:231-268): NoteOn = GateOn + freq_ = mtof(note) + Retrigger(true) on both
+// envelopes (:245-251); NoteOff / GateOff = gate off (:236-239, :253-256); GateOn = gate on
+// (:231-234); SetFrequency = freq_ (:264-267).  The last gate call decides the gate, any NoteOn
+// retriggers (gate calls do not touch the envelope modes), the last NoteOn / SetFrequency the pitch.
+void Shadow::fold_events() {
+    folded.clear();
+    for (const olfx_voice_event &ev : events) {
+        int32_t &k = ev_slot[ev.inst];
+        if (k < 0) {
+            k = (int32_t)folded.size();
+            folded.push_back(Folded{ev.inst, 0u, 0u, 0u});
+        }
+        Folded &r = folded[(size_t)k];
+        switch (ev.type) {
+        case OLFX_EV_NOTE_ON: {
+            r.op |= VEV_GATE_SET | VEV_GATE_ON | VEV_RETRIGGER | VEV_FREQ;
+            const float hz = mtof_note(ev.note);                              // daisysp::mtof
+            std::memcpy(&r.freq, &hz, 4);
+            break;
+        }
+        case OLFX_EV_GATE_ON: r.op |= VEV_GATE_SET | VEV_GATE_ON; break;
+        case OLFX_EV_SET_FREQUENCY:
+            r.op |= VEV_FREQ;
+            std::memcpy(&r.freq, &ev.value, 4);
+            break;
+        default: r.op = (r.op | VEV_GATE_SET) & ~VEV_GATE_ON; break;   // NoteOff / GateOff
+        }
+    }
+    events.clear();
+    // records per workgroup (64 voices); crowded workgroups (more than kVevCap records) get a run
+    // of the overflow list each, in group order
+    const uint32_t groups = (n + 63u) / 64u;
+    ev_count.assign(groups, 0u);
+    for (const Folded &r : folded) {
+        ev_count[r.inst >> 6]++;
+        ev_slot[r.inst] = -1;
+    }
+    ev_more.assign(groups, 0u);
+    n_more = 0;
+    for (uint32_t g = 0; g < groups; ++g)
+        if (ev_count[g] > kVevCap) {
+            ev_more[g] = n_more;
+            n_more += ev_count[g];
+        }
+}
+
+// The folded records into a packet's event section (VoiceArgs::ev layout, olfx_internal.h):
+// `fix` = [groups][kVevCap] 8-B slots, then the overflow list.
+void Shadow::write_events(uint32_t *fix) {
+    const uint32_t groups = (n + 63u) / 64u;
+    std::memset(fix, 0, (size_t)groups * kVevCap * 8);
+    uint32_t *more = fix + (size_t)groups * kVevCap * 2;
+    ev_fill.assign(groups, 0u);
+    for (const Folded &r : folded) {
+        const uint32_t g = r.inst >> 6;
+        const uint32_t k = ev_fill[g]++;
+        uint32_t *rec = ev_count[g] <= kVevCap ? fix + 2 * ((size_t)g * kVevCap + k) : more + 2 * ((size_t)ev_more[g] + k);
+        rec[0] = (r.inst & 63u) | r.op << 8;
+        rec[1] = r.freq;
+    }
+    for (uint32_t g = 0; g < groups; ++g)
+        if (ev_count[g] > kVevCap) {
+            fix[2 * (size_t)g * kVevCap] = VEV_MORE << 8 | ev_count[g] << 16;
+            fix[2 * (size_t)g * kVevCap + 1] = ev_more[g];
+        }
+}
+
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more) {
+    PacketPlan pl;
+    pl.dense = m == n;                                   // every instance: no instance list
+    pl.o_inst = 0;
+    pl.o_val = pl.o_inst + (pl.dense ? 0 : up4(m));
+    pl.o_ev = up4(pl.o_val + (size_t)W * m);
+    pl.words = pl.o_ev + (evs ? 2 * ((size_t)((n + 63u) / 64u) * kVevCap + n_more) : 0);
+    return pl;
+}
+
+size_t max_packet_words(int kind, uint32_t n_inst) {
+    const size_t n = n_inst, W = coef_segments(kind).total();
+    const size_t ev = is_voice_kind(kind) ? 2 * ((n + 63) / 64 * kVevCap + n) : 0;
+    return n + W * n + ev + 16;
+}
+
+void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
+    const size_t m = dirty_list.size();
+    const uint32_t W = coef_segments(kind).total();
+    uint32_t *val = buf + pl.o_val;
+    h_words.resize(W);
+    for (size_t r = 0; r < m; ++r) {
+        const uint32_t i = pl.dense ? (uint32_t)r : dirty_list[r];
+        if (!pl.dense) buf[pl.o_inst + r] = i;
+        derive_record(i, h_words.data());
+        for (uint32_t w = 0; w < W; ++w) val[(size_t)w * m + r] = h_words[w];
+    }
+    for (const uint32_t i : dirty_list) dirty_mark[i] = 0;
+    dirty_list.clear();
+}
+
+}  // namespace host
+}  // namespace olfx
+
+// =============================================================================================
+// C-ABI: the one entry point that needs no engine
+// =============================================================================================
+extern "C" int olfx_control_map(int kind, uint8_t control, int source, float value, uint32_t *field, float *param_value) {
+    using namespace olfx;
+    using namespace olfx::host;
+    if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
+    const bool midi = source == OLFX_CTL_MIDI;
+    // MIDI: ol::core::scale(val, 0, 127, lo, hi, power); hardware: scale(value, 0, 1, ...) or raw
+    auto sc = [&](float hi, float power) {
+        return midi ? core_scale(value, 0.f, 127.f, 0.f, hi, power) : core_scale(value, 0.f, 1.f, 0.f, hi, power);
+    };
+    const float unit = midi ? core_scale(value, 0.f, 127.f, 0.f, 1.f, 1.f) : value;   // `scaled` / raw value
+    auto put = [&](uint32_t f, float v) { *field = f; *param_value = v; return OLFX_OK; };
+    if (is_voice_kind(kind)) {                     // SynthVoice.h:100-229
+        switch (control) {
+        case CC_CTL_VOLUME: return put(OLFX_VC_AMP_ENV_AMOUNT, unit);
+        case CC_CTL_PORTAMENTO: return put(OLFX_VC_PORTAMENTO, sc(1.f, 4.f));
+        case CC_FILTER_CUTOFF: return put(OLFX_VC_FILTER_CUTOFF, sc(20000.f, 2.5f));
+        case CC_FILTER_RESONANCE: return put(OLFX_VC_FILTER_RESONANCE, unit);
+        case CC_FILTER_DRIVE: return put(OLFX_VC_FILTER_DRIVE, unit);
+        case CC_ENV_FILT_AMT: return put(OLFX_VC_FILTER_ENV_AMOUNT, unit);
+        case CC_ENV_FILT_A: return put(OLFX_VC_FILTER_ATTACK, unit);
+        case CC_ENV_FILT_D: return put(OLFX_VC_FILTER_DECAY, sc(1.f, 3.f));
+        case CC_ENV_FILT_S: return put(OLFX_VC_FILTER_SUSTAIN, unit);
+        case CC_ENV_FILT_R: return put(OLFX_VC_FILTER_RELEASE, unit);
+        case CC_ENV_AMP_A: return put(OLFX_VC_AMP_ATTACK, unit);
+        case CC_ENV_AMP_D: return put(OLFX_VC_AMP_DECAY, unit);
+        case CC_ENV_AMP_S: return put(OLFX_VC_AMP_SUSTAIN, unit);
+        case CC_ENV_AMP_R: return put(OLFX_VC_AMP_RELEASE, unit);
+        case CC_OSC_1_VOLUME: return put(OLFX_FIELD_UPDATE_ONLY, unit);   // osc_1_mix: unused by Process
+        default: return OLFX_IGNORED;
+        }
+    }
+    if (kind == OLFX_KIND_FXRACK) {                // FxRack -> FilterFx / DelayFx / ReverbFx
+        switch (control) {
+        case CC_FX_FILTER_CUTOFF: return put(OLFX_FR_FILTER_CUTOFF, midi ? sc(20000.f, 1.f) : sc(20000.f, 1.02f));
+        case CC_FX_FILTER_RESONANCE: return put(OLFX_FR_FILTER_RESONANCE, unit);
+        case CC_FX_FILTER_DRIVE: return put(OLFX_FR_FILTER_DRIVE, unit);
+        case CC_FX_FILTER_TYPE: return put(OLFX_FR_FILTER_TYPE, (float)(int32_t)sc(5.f, 1.f));   // FilterType(float)
+        case CC_DELAY_TIME: return put(OLFX_FR_DELAY_TIME, unit);
+        case CC_DELAY_FEEDBACK: return put(OLFX_FR_DELAY_FEEDBACK, unit);
+        case CC_DELAY_BALANCE: return put(OLFX_FR_DELAY_BALANCE, unit);
+        case CC_DELAY_CUTOFF:                      // DelayFx handles these in MIDI only (Fx.h:253-260)
+            return midi ? put(OLFX_FR_DELAY_CUTOFF, sc(20000.f, 1.f)) : OLFX_IGNORED;
+        case CC_DELAY_RESONANCE: return midi ? put(OLFX_FR_DELAY_RESONANCE, unit) : OLFX_IGNORED;
+        case CC_REVERB_BALANCE: return put(OLFX_FR_REVERB_BALANCE, unit);
+        case CC_CTL_VOLUME: return put(OLFX_FR_MASTER_VOLUME, unit);
+        default: return OLFX_IGNORED;              // incl. the reverb CCs that reach only the ReverbSc stub
+        }
+    }
+    return n_params_of(kind) ? OLFX_IGNORED : OLFX_E_KIND;
+}

@@ -1,0 +1,115 @@
+// ol_dsp_amd/csrc/olfx_host.h -- the host's control logic that touches neither the GPU nor a HIP
+// type: the kind tables, the reference's setter arithmetic (parameters -> coefficient words), the
+// host shadow of an engine's parameters with its validation and bookkeeping, and the format of the
+// control packet.  olfx_engine.cpp owns a Shadow by value and delivers the packets it fills;
+// tests/cpp/test_host_core.cpp drives the same code on the CPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/olfx.h"
+#include "olfx_layout.h"
+
+namespace olfx {
+namespace host __attribute__((visibility("hidden"))) {
+
+// ---- per-kind tables ----
+uint32_t n_params_of(int kind);              // 0: unknown kind
+uint32_t in_channels(int kind);
+uint32_t out_channels(int kind);
+void default_params(int kind, float *p);     // the reference's defaults of the user-facing parameters
+void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize);
+uint64_t state_bytes(int kind, uint32_t n, float sr);
+double algorithmic_bytes_per_frame(int kind);
+double algorithmic_read_bytes_per_frame(int kind);
+
+// ---- the reference setters: parameters [OLFX_*] -> coefficient words [*C_*] ----
+float core_scale(float in, float inlow, float inhigh, float outlow, float outhigh, float power);
+uint32_t dattorro_predelay_samples(float v);
+void derive_dattorro(const float *p, float *c);
+void derive_chorus(const float *p, double sr, uint32_t *c);
+void derive_pitchshift(const float *p, double sr, uint32_t *c);
+void derive_fxrack(const float *p, float sr, uint32_t *c);
+void derive_voice(const float *p, bool configured, bool moog, float sr, float *c);
+
+// An instance's coefficient record: the words of each destination array (field-major on the
+// device, CoefScatterArgs), in record order.
+struct Segments {
+    uint32_t nseg, words[3];
+    uint32_t total() const { return words[0] + words[1] + words[2]; }
+};
+Segments coef_segments(int kind);
+
+// ---- the control packet (u32 words, 16-B aligned sections) ----
+// instance list (absent when every instance changed: dense) | coefficient records [W][m] | event
+// slots [groups][kVevCap] and the overflow list, 8-B records (write_events)
+struct PacketPlan {
+    bool dense;
+    size_t o_inst, o_val, o_ev, words;
+};
+// n instances of which m changed, W words per record, `evs`: an event section with n_more
+// overflow records
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more);
+// The largest packet an engine can produce: every instance's coefficients and, for voices, an
+// event for every voice (plan_packet's layout, rounded up).
+size_t max_packet_words(int kind, uint32_t n);
+
+struct Folded { uint32_t inst, op, freq, pad; };
+
+// The host shadow of an engine: what the caller has set, what of it the device has yet to see, and
+// the note events queued for the next block.  Every operation that can refuse returns OLFX_OK or
+// an OLFX_E_* code with the reason in `msg`, and a refused call changes nothing.
+struct Shadow {
+    int kind = 0;
+    uint32_t n = 0, n_params = 0;
+    float sr = 48000.f;
+    std::vector<float> params;            // [n_params][n]
+    std::vector<uint8_t> configured;      // voice: UpdateConfig seen
+    // instances whose coefficients must be re-derived at the next block (each listed once)
+    std::vector<uint32_t> dirty_list;
+    std::vector<uint8_t> dirty_mark;
+    int64_t n_components = 0;             // rack instances with OLFX_FR_TOPOLOGY >= 2
+    bool pre_changed = true;              // a reverb pre-delay changed since the flag was last cleared
+    std::vector<olfx_voice_event> events; // queued for the next block
+    std::vector<Folded> folded;           // fold_events: one record per voice, by first appearance
+    // per workgroup: records, first overflow record (crowded groups), records written so far
+    std::vector<uint32_t> ev_count, ev_more, ev_fill;
+    uint32_t n_more = 0;                  // overflow records
+    std::vector<int32_t> ev_slot;         // voice -> its record in `folded` during fold_events, else -1
+    std::vector<uint32_t> h_words;        // scratch for a record
+    char msg[160] = "";
+
+    void init(int kind_, uint32_t n_, float sr_) { kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_); }
+    // Every instance at the reference's defaults, unconfigured, all dirty; nothing queued.
+    void reset();
+
+    int set_range(uint32_t first, uint32_t count, uint32_t field0, uint32_t n_fields, const float *values);
+    int set_list(uint32_t field, const uint32_t *inst, const float *values, uint32_t count);
+    int set_member(uint32_t inst, uint32_t field, float value);
+    int update(uint32_t first, uint32_t count);
+    int control(const olfx_control_event *ev, uint32_t count);       // rack topology routing included
+    int note_events(const olfx_event *ev, uint32_t count);
+    int voice_events(const olfx_voice_event *ev, uint32_t count);
+    bool uniform_predelay() const;        // reverb: every instance has the same pre-delay in samples
+
+    // The coefficient record of instance i from its current parameters, in coef_segments' order.
+    void derive_record(uint32_t i, uint32_t *w) const;
+    // The queued events as one record per voice (`folded`) and their place in the event section.
+    void fold_events();
+    PacketPlan plan(bool evs) const { return plan_packet(n, dirty_list.size(), coef_segments(kind).total(), evs, n_more); }
+    // The plan's instance list and field-major records into `buf`; clears the dirty list.
+    void fill_records(const PacketPlan &pl, uint32_t *buf);
+    // The folded records into the event section `fix` (buf + o_ev).
+    void write_events(uint32_t *fix);
+
+private:
+    int fail(int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+    const char *bad_value(uint32_t field, float v) const;
+    void store_param(uint32_t field, uint32_t inst, float v);
+    void mark_dirty(uint32_t first, uint32_t count);
+};
+
+}  // namespace host
+}  // namespace olfx

@@ -41,6 +41,17 @@ def test_cpp_block_adapter_host_logic():
     assert "4 tests, 0 failures" in r.stdout
 
 
+def test_cpp_host_core():
+    """The engine's HIP-free host core (ol_dsp_amd/csrc/olfx_host.cpp) linked into a stand-alone
+    program: note-event folding, the event section's fixed slots and overflow list, packet
+    layout, the setters' coefficient words, rejected calls and the rack's CC routing."""
+    _build()
+    r = subprocess.run([os.path.join(CPP, "test_host_core")], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "7 tests, 0 failures" in r.stdout
+
+
 @pytest.mark.gpu
 def test_cpp_operators_on_gpu():
     _build()

@@ -7,6 +7,9 @@
   tests/cpp/test_adapter_asan     the per-frame -> block adapter's host logic (include/olfx_adapter.hpp)
                                   under ASan + UBSan
   tests/cpp/test_adapter_tsan     the same under TSan, including Queue() from a second thread
+  tests/cpp/test_host_core_asan   the engine's HIP-free host core (ol_dsp_amd/csrc/olfx_host.cpp:
+                                  validation, coefficient derivation, control-packet layout)
+                                  under ASan + UBSan
 
 Any sanitizer report aborts the binary (-fno-sanitize-recover=all) or is matched below.
 """
@@ -48,3 +51,10 @@ def test_adapter_under_sanitizers(kind):
     out = _run(os.path.join(ROOT, "tests", "cpp", f"test_adapter_{kind}"),
                {"UBSAN_OPTIONS": "print_stacktrace=1", "TSAN_OPTIONS": "halt_on_error=1"})
     assert "4 tests, 0 failures" in out
+
+
+def test_host_core_under_asan_ubsan():
+    _make("tests/cpp", "test_host_core_asan")
+    out = _run(os.path.join(ROOT, "tests", "cpp", "test_host_core_asan"),
+               {"ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    assert "7 tests, 0 failures" in out
