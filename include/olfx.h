@@ -64,10 +64,15 @@ enum {
     OLFX_KIND_VOICE      = 4,  /* synthlib SynthVoice: polyBLEP saw -> SVF LP (env cutoff) -> amp env; mono out */
     OLFX_KIND_CHAIN      = 5,  /* fused chorus -> pitch-shift -> dattorro, stereo */
     OLFX_KIND_FXRACK     = 6,  /* fxlib ol::fx::FxRack<2>: delay -> reverb -> filter -> master (Fx.h:398-492) */
-    OLFX_KIND_VOICE_MOOG = 7   /* SynthVoice(OscillatorSoundSource, MoogFilter): the Daisy synth firmware voice
+    OLFX_KIND_VOICE_MOOG = 7,  /* SynthVoice(OscillatorSoundSource, MoogFilter): the Daisy synth firmware voice
                                   (ol_daisy/app/synth/main.cpp:49-52); daisysp::LadderFilter LP24 in place of the
                                   SVF (Filter.h:35-63).  Same OLFX_VC_* parameters (FILTER_DRIVE is ignored:
                                   MoogFilter::SetDrive is a no-op), note events and control changes. */
+    OLFX_KIND_PLATERACK  = 8   /* the effect rack with the Dattorro plate as its reverb stage: DelayFx<2> ->
+                                  Dattorro((a0 + a1) / 2) mixed by REVERB_BALANCE -> FilterFx<2> -> master, one
+                                  launch (platerack.hip).  The stage the reference's rack was written for: its
+                                  ol::fx::Reverb interface (Reverb.h:44-65) is the DattorroVerb_set* list and
+                                  ReverbFx.cpp:11-37 still holds the glue, commented out.  OLFX_PR_* fields. */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -147,6 +152,29 @@ enum {
 #define OLFX_CN_VERB0     (OLFX_CH_NPARAMS + OLFX_PS_NPARAMS)
 #define OLFX_CN_NPARAMS   (OLFX_CH_NPARAMS + OLFX_PS_NPARAMS + OLFX_DT_NPARAMS)
 
+/* Plate rack: the rack's fields (OLFX_FR_*), then the plate's (OLFX_DT_*, what the verb.h setters take,
+   validated as OLFX_KIND_DATTORRO validates them; a pre-delay change lands at the next block boundary).
+   OLFX_FR_TOPOLOGY is 0 (FxRack<2>::Process) or 1 (the firmware callback: DelayFx<1>, stereo[0] = stereo[1],
+   the reverb, FilterFx<2> in place -- channel 1 keeps the plate's right output mixed with the dry signal --
+   and no master volume); 2..4 are refused.
+   Defaults.  Rack fields: as OLFX_KIND_FXRACK.  Plate fields: what ReverbFx::Init -> Update() would hand
+   the plate through the glue of ReverbFx.cpp:29-37 wherever the ReverbFx member (Fx.h:274-281) lies in the
+   setter's domain: decay_time 0.5 -> setDecay, pre_cutoff 0.5 -> setPreFilter, input_diffusion1 / 2 0.5,
+   decay_diffusion 0.5.  The member `cutoff` is 12000, a frequency in Hz meant for ReverbSc::SetLpFreq and
+   outside setDamping's [0, 1], and the glue never calls setPreDelay: DAMPING (0.95) and PREDELAY (0.1) keep
+   DattorroVerb_create's own defaults (verb.cpp:215-221).
+   Controls (olfx_control_map / olfx_control): ReverbFx::UpdateMidiControl / UpdateHardwareControl
+   (Fx.h:313-391) composed with that glue: CC_REVERB_TIME -> DECAY, CC_REVERB_PREFILTER -> PREFILTER,
+   CC_REVERB_INPUT_DIFFUSION_1 -> INPUT_DIFFUSION1, CC_REVERB_DECAY_DIFFUSION and (the reference's quirk,
+   Fx.h:323-324, kept) CC_REVERB_INPUT_DIFFUSION_2 -> DECAY_DIFFUSION, CC_REVERB_BALANCE -> REVERB_BALANCE,
+   CC_REVERB_CUTOFF -> DAMPING in the 0..1 form (`//cutoff = scaled`, Fx.h:328; the live Hz form addresses
+   ReverbSc), CC_REVERB_PREDELAY and CC_EARLY_PREDELAY -> OLFX_FIELD_UPDATE_ONLY (the glue forwards
+   neither).  MIDI values are scaled 0..1, hardware values taken as given.  Delay, filter and volume
+   controls and the topology-1 routing: as OLFX_KIND_FXRACK. */
+#define OLFX_PR_RACK0     0
+#define OLFX_PR_VERB0     (OLFX_FR_NPARAMS)
+#define OLFX_PR_NPARAMS   (OLFX_FR_NPARAMS + OLFX_DT_NPARAMS)
+
 /* ---- note events (voices) ----
    The ol::synth::Voice calls that change a voice's gate or pitch (Voice.h:33-57), as SynthVoice
    implements them (SynthVoice.h:231-268):
@@ -181,6 +209,7 @@ typedef struct olfx_voice_event {
                        DelayFx / ReverbFx / FilterFx handlers it forwards to (Fx.h:116-163, 218-267, 313-391);
                        olfx_control_map gives topology 0's mapping, olfx_control uses each instance's
                        topology (OLFX_FR_TOPOLOGY 1: the firmware's direct FilterFx routing)
+     OLFX_KIND_PLATERACK: the rack's, with the reverb CCs reaching the plate (the table at OLFX_PR_*)
    Controls the reference ignores for a kind (its `default: update = false`) are skipped. */
 enum { OLFX_CTL_MIDI = 0, OLFX_CTL_HARDWARE = 1 };
 #define OLFX_IGNORED 1                 /* olfx_control_map: the reference ignores this control */

@@ -191,6 +191,30 @@ public:
        filter in place, no master) */
     enum class Topology { Rack = 0, DaisyFirmware = 1 };
     void SetTopology(uint32_t i, Topology t) { set(i, OLFX_FR_TOPOLOGY, static_cast<float>(t)); }
+
+protected:
+    FxRackBank(int kind, uint32_t n_inst, float sample_rate, uint32_t block, int device)
+        : Engine(kind, n_inst, sample_rate, block, device) {}
+};
+
+/* The rack with the Dattorro plate as its reverb stage (OLFX_KIND_PLATERACK): DelayFx -> plate on
+   (a0 + a1) / 2, mixed by the reverb balance -> FilterFx -> master volume, one launch.  FxRackBank's
+   methods (both topologies; UpdateMidiControl / UpdateHardwareControl reach the plate through the
+   reverb CCs, include/olfx.h OLFX_PR_*) plus ol::fx::Reverb's seven setters (Reverb.h:44-65), which
+   take what the verb.h setters take.  In topology 1 channel 1 is the plate's right output mixed with
+   the dry signal. */
+class PlateRackBank : public FxRackBank {
+public:
+    PlateRackBank(uint32_t n_inst, float sample_rate, uint32_t block = 256, int device = 0)
+        : FxRackBank(OLFX_KIND_PLATERACK, n_inst, sample_rate, block, device) {}
+    /* a change lands at the next block boundary, per instance */
+    void SetPredelay(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_PREDELAY, v); }
+    void SetPrefilter(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_PREFILTER, v); }
+    void SetInputDiffusion1(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION1, v); }
+    void SetInputDiffusion2(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION2, v); }
+    void SetDecayDiffusion(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION, v); }
+    void SetDecay(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DECAY, v); }
+    void SetDamping(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DAMPING, v); }
 };
 
 /* ol::synth::SynthVoice over N voices (SynthVoice.h). The config array is in Voice::Config field

@@ -30,6 +30,7 @@ KIND_VOICE = 4
 KIND_CHAIN = 5
 KIND_FXRACK = 6
 KIND_VOICE_MOOG = 7
+KIND_PLATERACK = 8
 
 IO_DEVICE = 0
 IO_HOST = 1

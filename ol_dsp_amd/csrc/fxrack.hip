@@ -31,71 +31,26 @@
 // chunks before it: the last two chunks' writes are patched in from registers -- so every delay
 // 0..47999 takes the same branch-free path.
 // Bound: HBM (32 B per stereo frame: ring write 8 + ring read 8 + I/O 16).
-#include <type_traits>
-#include <utility>
-
-#include "chorus_stage.h"
+#include "rack_delay_stage.h"
 
 namespace olfx {
 
 namespace {
 
+// the delay stage's window machinery, the Svf tick and static_for: rack_delay_stage.h (shared with
+// platerack.hip)
+using fr::static_for;
+using fr::svf_tick;
+using fr::wave_lds_order;
 constexpr int kFrThreads = 256;
-constexpr int kFrChunk = 16;
-constexpr int kFrWin = 20;                          // window slots (18 read) staged from two lines
-constexpr int kFrSlots = kFrWin + 1;                // + junk slot
-constexpr int kFrStride = 36;                       // staging floats per instance (32 + pad)
+constexpr int kFrChunk = fr::kChunk;
+constexpr int kFrWin = fr::kWin;                    // window slots (18 read) staged from two lines
+constexpr int kFrSlots = fr::kSlots;                // + junk slot
+constexpr int kFrStride = fr::kStride;              // staging floats per instance (32 + pad)
 constexpr int kFrOutCh = 16 * 32 + 32;              // output staging [ch][frame][instance], per channel
 // floats of LDS per wave: the window, the ring-run staging (which also transposes the cooperative
 // input rows) and, with cooperative I/O, the output staging
-constexpr int kFrRegion = kFrSlots * 64 + 32 * kFrStride + 2 * kFrOutCh;
-__device__ __forceinline__ void wave_lds_order() {   // one wave's LDS writes before its other lanes' reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Svf::Process (DaisySP, double-sampled Chamberlin) returning the selected output
-// (0 low, 1 band, 2 high, 3 notch, 4 peak), as oracle/fxrack_ref.c.  Each output is the mean of its
-// two passes' values, 0.5 x1 + 0.5 x2: the pass's value is selected first and only the selected
-// output is formed (the same operations for it; the reference forms all five)
-__device__ __forceinline__ float svf_pick(uint32_t type, float low, float band, float high, float notch) {
-    float peak = low - high;
-    asm volatile("" : "+v"(peak));                  // computed for every lane: selects, not branches
-    float r = type == 4 ? peak : low;
-    r = type == 3 ? notch : r;
-    r = type == 2 ? high : r;
-    return type == 1 ? band : r;
-}
-__device__ __forceinline__ float svf_tick(float in, float freq, float damp, float drive, uint32_t type,
-                                          float &low, float &band) {
-    float notch = in - damp * band;
-    low = low + freq * band;
-    float high = notch - low;
-    band = freq * high + band - drive * band * band * band;
-    const float x1 = svf_pick(type, low, band, high, notch);
-    notch = in - damp * band;
-    low = low + freq * band;
-    high = notch - low;
-    band = freq * high + band - drive * band * band * band;
-    const float x2 = svf_pick(type, low, band, high, notch);
-    return 0.5f * x1 + 0.5f * x2;
-}
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>), unrolled at compile time
-template <class F, int... K>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, K...>) {
-    (f(std::integral_constant<int, K>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ uint32_t wrap48k(int64_t p) {
-    const int64_t m = p % (int64_t)kFrMaxDelay;
-    return (uint32_t)(m < 0 ? m + kFrMaxDelay : m);
-}
+constexpr int kFrRegion = fr::kRegion + 2 * kFrOutCh;
 
 }  // namespace
 
@@ -160,7 +115,6 @@ __global__ __launch_bounds__(kFrThreads) void fxrack_block_v3(FxRackArgs a) {
     const uint32_t io_v = ch * (uint32_t)a.plane * 4u + i * 4u, frame_b = n * 4u;
     // lane F holds channel 0's output, lane D channel 1's (0): each stores the other plane
     const uint32_t out_v = valid ? (1u - ch) * (uint32_t)a.plane * 4u + i * 4u : 0xFFFFFFF0u;
-    constexpr uint32_t kRing = kFrMaxDelay * 8u;        // bytes per instance ring
 
     float *win = lds + wib * kFrRegion;                 // [kFrSlots][64]
     float *wcol = win + lane;
@@ -192,45 +146,8 @@ __global__ __launch_bounds__(kFrThreads) void fxrack_block_v3(FxRackArgs a) {
         wave_lds_order();
     };
 
-    // window of the chunk starting at t: first position (t - D - 1) rounded down to even, as an
-    // offset from t -- the same for every chunk (t is even)
-    auto rel_of = [&](uint32_t t) { return (int)(((int64_t)t - (int64_t)D - 1) & ~(int64_t)1) - (int)t; };
-    // Cooperative line loads: piece P = r * 64 + lane of 256 -> piece m = 2 r + lane / 32 (16 B:
-    // positions 2m, 2m + 1 of the line) of instance jj = lane % 32 (instances innermost: a
-    // ds_write_b64 lane group of 16 contiguous lanes stages one piece of 16 instances, 16 distinct
-    // bank pairs, conflict-free).  Every part of a lane serves the same instance jj, whose window
-    // start (ring position, wrapped) comes from lane 2 jj once per launch.
-    const uint32_t jj = lane & 31u;
-    const uint32_t oj = min(inst0 + jj, n - 1) - inst0;      // ring within the wave's descriptor
-    const uint32_t spos = (uint32_t)__builtin_amdgcn_ds_bpermute(
-        (int)(jj << 3), (int)wrap48k(((int64_t)a.t0 - (int64_t)D - 1) & ~(int64_t)1));
-    const uint32_t so15 = spos & 15u;                   // window start within its line (even)
-    uint32_t lcur = spos >> 4;                          // line L of the current chunk (instance jj)
-    constexpr uint32_t kLines = kFrMaxDelay / 16u;      // 3000 lines per ring: wraps at a line edge
-    float4 lo[4], nx[4];                                // lines L (carried) and L + 1 (loaded a chunk back)
-    auto load_line = [&](float4 (&dst)[4], uint32_t line) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            dst[r] = ch::ld4(rR, oj * kRing + line * 128u + ((uint32_t)r * 2u + (lane >> 5)) * 16u);
-    };
-    auto next_line = [&](uint32_t l) { return l + 1u == kLines ? 0u : l + 1u; };
-    auto stage_lines = [&]() {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = r * 2 + (int)(lane >> 5);
-            const int slo = 2 * m - (int)so15, shi = slo + 16;   // slots of the piece in L, L + 1
-            if (slo >= 0) {
-                float *p = win + (uint32_t)slo * 64u + 2u * jj;
-                *(float2 *)p = make_float2(lo[r].x, lo[r].y);
-                *(float2 *)(p + 64) = make_float2(lo[r].z, lo[r].w);
-            }
-            if (shi < kFrWin) {                         // shi + 1 <= kFrWin: the junk slot at most
-                float *p = win + (uint32_t)shi * 64u + 2u * jj;
-                *(float2 *)p = make_float2(nx[r].x, nx[r].y);
-                *(float2 *)(p + 64) = make_float2(nx[r].z, nx[r].w);
-            }
-        }
-    };
+    // the window's lines and their staging: rel_of, lo / nx / lcur, load_line, next_line, stage_lines
+    FR_DELAY_LINES(rR, n, inst0, lane, D, a.t0, win);
 
     float x[kFrChunk], xn[kFrChunk], y[kFrChunk], y2[kFrChunk];
     const uint32_t t00 = a.t0;                          // ring position of frame 0
@@ -252,15 +169,7 @@ __global__ __launch_bounds__(kFrThreads) void fxrack_block_v3(FxRackArgs a) {
     // expose the stores' round trip once per chunk.
     float o[kFrChunk];
     auto flush = [&](uint32_t fp, int Cp) {             // the stores of the chunk at frame fp
-        const uint32_t tp = t00 + fp;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t q = (uint32_t)r * 64u + lane, oo = q >> 3, f2 = 2u * (q & 7u);
-            const float4 vv = *(const float4 *)(stage + oo * kFrStride + 2u * f2);
-            const uint32_t oi = inst0 + oo;
-            const bool ok = oi < n && (int)f2 < Cp;     // else an offset past the buffer: dropped
-            ch::st4(rR, ok ? oo * kRing + wrap48k((int64_t)tp + f2) * 8u : 0xFFFFFFF0u, vv);
-        }
+        FR_FLUSH_RING(rR, n, inst0, lane, t00, stage, fp, Cp)
         if constexpr (COOP) {
             // the outputs, staged [ch][frame][instance] by the chunk (lane ch holds plane 1 - ch)
 #pragma unroll
@@ -284,22 +193,7 @@ __global__ __launch_bounds__(kFrThreads) void fxrack_block_v3(FxRackArgs a) {
         // ---- 1. this chunk's window -> LDS from its two lines, patched with the last two chunks'
         //         writes: line L was loaded before chunk c-2's stores, L + 1 before chunk c-1's ----
         stage_lines();
-        // (only delays below 2 chunks + a window reach those positions: skipped wave-uniformly
-        // otherwise; rel = -D - 1 or -D - 2)
-        if (f0 >= 2u * kFrChunk && __builtin_amdgcn_ballot_w64(-2 * kFrChunk - rel < kFrWin)) {
-#pragma unroll
-            for (int k = 0; k < kFrChunk; ++k) {
-                const int s = k - 2 * kFrChunk - rel;   // slot of position t - 32 + k
-                if (s >= 0 && s < kFrWin) wcol[s * 64] = y2[k];
-            }
-        }
-        if (f0 > 0 && __builtin_amdgcn_ballot_w64(-kFrChunk - rel < kFrWin)) {
-#pragma unroll
-            for (int k = 0; k < kFrChunk; ++k) {
-                const int s = k - kFrChunk - rel;       // slot of position t - 16 + k
-                if (s >= 0 && s < kFrWin) wcol[s * 64] = y[k];
-            }
-        }
+        FR_PATCH_WINDOW(f0, rel, wcol, y, y2)
         if (f0 > 0) flush(f0 - kFrChunk, kFrChunk);     // the previous chunk was full
         // ---- 2. the next chunk's inputs and new line in flight (unconditional); L + 1 is carried ----
         if constexpr (COOP) {
@@ -312,10 +206,7 @@ __global__ __launch_bounds__(kFrThreads) void fxrack_block_v3(FxRackArgs a) {
                 xn[k] = k < Cn ? vv : 0.f;
             }
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lo[r] = nx[r];
-        lcur = next_line(lcur);
-        load_line(nx, next_line(lcur));
+        FR_CARRY_LINES();
 #pragma unroll
         for (int k = 0; k < kFrChunk; ++k) y2[k] = y[k];
         // ---- 3. the frames: C + 1 ticks; tick k runs frame k's delay line (both lanes, own

@@ -114,7 +114,7 @@ struct olfx_engine {
     uint32_t *fr_state = nullptr, *fr_coef = nullptr;
 
     // dattorro (also the chain's reverb stage)
-    uint32_t n_dt = 0;           // reverb-stage instances: n, or n rounded up to 64 for the chain
+    uint32_t n_dt = 0;           // reverb-stage instances: n, or n rounded up to 64 for the chain and the plate rack
     float *dt_rings = nullptr;
     float *dt_state = nullptr;
     float *dt_coef = nullptr;
@@ -181,12 +181,12 @@ size_t carve(olfx_engine *e, char *base) {
     };
     const int kind = e->kind;
     const size_t n = e->n, nd = e->n_dt;
-    if (kind == OLFX_KIND_FXRACK) {
+    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK) {
         take(e->fr_ring, (size_t)kFrMaxDelay * 2 * n * 4);
         take(e->fr_state, (size_t)FRS_N * n * 4);
         take(e->fr_coef, (size_t)FRC_N * n * 4);
     }
-    if (kind == OLFX_KIND_DATTORRO || kind == OLFX_KIND_CHAIN) {
+    if (kind == OLFX_KIND_DATTORRO || kind == OLFX_KIND_CHAIN || kind == OLFX_KIND_PLATERACK) {
         take(e->dt_rings, (size_t)dt_total_floats() * nd * 4);
         take(e->dt_state, (size_t)DTS_N * nd * 4);
         take(e->dt_coef, (size_t)DTC_N * nd * 4);
@@ -229,6 +229,9 @@ uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
         dst[0] = e->ch_coef; dst[1] = e->ps_coef; dst[2] = e->dt_coef; stride[2] = e->n_dt;
         break;
     case OLFX_KIND_FXRACK: dst[0] = e->fr_coef; break;
+    case OLFX_KIND_PLATERACK:   // padding plate instances keep their zeroed coefficients
+        dst[0] = e->fr_coef; dst[1] = e->dt_coef; stride[1] = e->n_dt;
+        break;
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: dst[0] = e->vc_coef; break;
     default: break;
@@ -539,6 +542,24 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_fxrack(a, s);
         break;
     }
+    case OLFX_KIND_PLATERACK: {
+        // one fused launch: the delay waves feed the plate wave and the filter wave through LDS.  Two
+        // clocks from the one frame count: the rack ring's position and the plate's 16-bit stream time
+        PlateRackArgs a{};
+        a.ring = e->fr_ring;
+        a.state = e->fr_state;
+        a.coef = e->fr_coef;
+        a.d = dt_args(nullptr, nullptr);
+        a.in = din;
+        a.out = dout;
+        a.plane = plane;
+        a.n = e->n;
+        a.n_frames = n_frames;
+        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
+        a.cus = (uint32_t)e->cus;
+        r = launch_platerack(a, s);
+        break;
+    }
     case OLFX_KIND_CHAIN: {
         // one fused launch: chorus and pitch-shift waves feed the reverb wave through LDS
         ChainArgs a{};
@@ -563,7 +584,7 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
 // Kinds whose kernels address the audio planes with 32-bit buffer offsets from `in` / `out`.
 bool planes_32bit(int kind) {
     return kind == OLFX_KIND_CHORUS || kind == OLFX_KIND_PITCHSHIFT || kind == OLFX_KIND_CHAIN ||
-           kind == OLFX_KIND_FXRACK;
+           kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK;
 }
 
 // All n_frames of a call, as frame tiles where a launch's planes would leave the kernels' 32-bit
@@ -674,7 +695,7 @@ int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32
     if (const char *cb = std::getenv("OLFX_COPY_BYTES"))
         e->copy_bytes = std::min<size_t>((size_t)std::strtoull(cb, nullptr, 10), olfx_engine::kCopyBytes);
     host::chorus_sizes(sample_rate, &e->psize, &e->csize);
-    e->n_dt = kind == OLFX_KIND_CHAIN ? (n_inst + 63u) & ~63u : n_inst;
+    e->n_dt = kind == OLFX_KIND_CHAIN || kind == OLFX_KIND_PLATERACK ? (n_inst + 63u) & ~63u : n_inst;
 
     hipError_t r = hipSetDevice(device);
     if (r == hipSuccess) r = hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -980,6 +1001,7 @@ const char *olfx_kernel_name(const olfx_engine *e) {
     case OLFX_KIND_VOICE_MOOG: return "voice_block_v4";
     case OLFX_KIND_CHAIN: return "chain_block_v5";
     case OLFX_KIND_FXRACK: return "fxrack_block_v3";
+    case OLFX_KIND_PLATERACK: return "platerack_block_v1";
     default: return "";
     }
 }

@@ -22,6 +22,9 @@ uint32_t pow2_at_least(uint32_t x) {
 
 float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+// the most parameters a kind has (an instance's parameters on the stack)
+constexpr uint32_t kMaxParams = std::max({(uint32_t)OLFX_CN_NPARAMS, (uint32_t)OLFX_VC_NPARAMS, (uint32_t)OLFX_PR_NPARAMS});
+
 // a fraction of a cycle in [0, 1] as 64-bit fixed point (2^64 = one cycle); 1.0 wraps to 0
 uint64_t fix64(double cycles) {
     constexpr double kTwo64 = 18446744073709551616.0;
@@ -51,6 +54,7 @@ uint32_t n_params_of(int kind) {
     case OLFX_KIND_VOICE_MOOG: return OLFX_VC_NPARAMS;
     case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
     case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
+    case OLFX_KIND_PLATERACK: return OLFX_PR_NPARAMS;
     default: return 0;
     }
 }
@@ -136,6 +140,18 @@ void default_params(int kind, float *p) {
         p[OLFX_FR_MASTER_VOLUME] = 0.8f;
         p[OLFX_FR_TOPOLOGY] = 0.f;
         break;
+    case OLFX_KIND_PLATERACK:
+        default_params(OLFX_KIND_FXRACK, p + OLFX_PR_RACK0);
+        // the plate as ReverbFx::Init -> Update() would set it through the glue of ReverbFx.cpp:29-37
+        // (members Fx.h:274-281) where the member lies in the setter's domain; `cutoff` (12000 Hz, for
+        // ReverbSc) does not and setPreDelay is never called: verb.cpp:215-221 for those two
+        default_params(OLFX_KIND_DATTORRO, p + OLFX_PR_VERB0);
+        p[OLFX_PR_VERB0 + OLFX_DT_PREFILTER] = 0.5f;          // pre_cutoff
+        p[OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION1] = 0.5f;   // input_diffusion1
+        p[OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION2] = 0.5f;   // input_diffusion2
+        p[OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION] = 0.5f;    // decay_diffusion
+        p[OLFX_PR_VERB0 + OLFX_DT_DECAY] = 0.5f;              // decay_time
+        break;
     default: break;
     }
 }
@@ -161,6 +177,8 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
     case OLFX_KIND_VOICE_MOOG: return vc * n + (uint64_t)(VCS_N_MOOG - VCS_N) * 4 * n;
     case OLFX_KIND_CHAIN: return (dt + 2 * ch) * n;
     case OLFX_KIND_FXRACK: return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n;
+    case OLFX_KIND_PLATERACK:       // the rack's ring + the plate's, the plate's instances padded to 64
+        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n + dt * ((n + 63u) & ~63u);
     default: return 0;
     }
 }
@@ -175,6 +193,7 @@ double algorithmic_bytes_per_frame(int kind) {
     case OLFX_KIND_VOICE_MOOG: return 5.7;     // 4 B out + per-block state (9 more state words)
     case OLFX_KIND_CHAIN: return 228.6;
     case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
+    case OLFX_KIND_PLATERACK: return 32.0 + 164.6 - 16.0;   // rack + plate - the plate's own I/O (in LDS now)
     default: return 0.0;
     }
 }
@@ -190,6 +209,7 @@ double algorithmic_read_bytes_per_frame(int kind) {
     case OLFX_KIND_VOICE_MOOG: return 0.85;
     case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
     case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
+    case OLFX_KIND_PLATERACK: return 16.0 + 6445.0 * 4.0 / 256.0;   // rack + the plate's taps (its input is in LDS)
     default: return 0.0;
     }
 }
@@ -392,6 +412,7 @@ Segments coef_segments(int kind) {
     case OLFX_KIND_PITCHSHIFT: return {1, {CHC_N, 0, 0}};
     case OLFX_KIND_CHAIN: return {3, {CHC_N, CHC_N, DTC_N}};       // chorus, pitch-shift, reverb
     case OLFX_KIND_FXRACK: return {1, {FRC_N, 0, 0}};
+    case OLFX_KIND_PLATERACK: return {2, {FRC_N, DTC_N, 0}};       // rack, plate
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
     default: return {0, {0, 0, 0}};
@@ -399,7 +420,7 @@ Segments coef_segments(int kind) {
 }
 
 void Shadow::derive_record(uint32_t i, uint32_t *w) const {
-    float p[OLFX_CN_NPARAMS > OLFX_VC_NPARAMS ? OLFX_CN_NPARAMS : OLFX_VC_NPARAMS];
+    float p[kMaxParams];
     for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
     static_assert((int)VCC_N >= (int)DTC_N, "fc holds either kind's float coefficients");
     float fc[VCC_N];
@@ -417,6 +438,11 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
         std::memcpy(w + 2 * CHC_N, fc, DTC_N * 4);
         break;
     case OLFX_KIND_FXRACK: derive_fxrack(p, sr, w); break;
+    case OLFX_KIND_PLATERACK:
+        derive_fxrack(p + OLFX_PR_RACK0, sr, w);
+        derive_dattorro(p + OLFX_PR_VERB0, fc);
+        std::memcpy(w + FRC_N, fc, DTC_N * 4);
+        break;
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG:
         derive_voice(p, configured[i] != 0, kind == OLFX_KIND_VOICE_MOOG, sr, fc);
@@ -439,7 +465,7 @@ int Shadow::fail(int code, const char *fmt, ...) {
 
 void Shadow::reset() {
     params.assign((size_t)n_params * n, 0.f);
-    float d[OLFX_CN_NPARAMS > OLFX_VC_NPARAMS ? OLFX_CN_NPARAMS : OLFX_VC_NPARAMS];
+    float d[kMaxParams];
     default_params(kind, d);
     for (uint32_t f = 0; f < n_params; ++f)
         std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
@@ -467,10 +493,14 @@ const char *Shadow::bad_value(uint32_t field, float v) const {
     // the reference converts value * MAX_PREDELAY (4800) to uint16 (verb.cpp:137-139): values whose
     // product leaves [0, 65536) have no defined meaning there
     const bool predelay = (kind == OLFX_KIND_DATTORRO && field == OLFX_DT_PREDELAY) ||
-                          (kind == OLFX_KIND_CHAIN && field == OLFX_CN_VERB0 + OLFX_DT_PREDELAY);
+                          (kind == OLFX_KIND_CHAIN && field == OLFX_CN_VERB0 + OLFX_DT_PREDELAY) ||
+                          (kind == OLFX_KIND_PLATERACK && field == OLFX_PR_VERB0 + OLFX_DT_PREDELAY);
     if (predelay && !(v >= 0.f && v * 4800.0f < 65536.0f)) return "pre-delay outside [0, 65536/4800)";
     if (kind == OLFX_KIND_FXRACK && field == OLFX_FR_TOPOLOGY && !(v >= 0.f && v <= 4.f && v == (float)(int)v))
         return "rack topology must be 0, 1, 2, 3 or 4";
+    // the components alone (2..4) are the firmware's objects around the ReverbSc stub: no plate in them
+    if (kind == OLFX_KIND_PLATERACK && field == OLFX_PR_RACK0 + OLFX_FR_TOPOLOGY && !(v == 0.f || v == 1.f))
+        return "plate rack topology must be 0 or 1";
     return nullptr;
 }
 
@@ -555,7 +585,9 @@ bool Shadow::uniform_predelay() const {
 namespace {
 enum : uint8_t {
     CC_CTL_PORTAMENTO = 5, CC_CTL_VOLUME = 7,
-    CC_REVERB_BALANCE = 34,
+    CC_REVERB_TIME = 32, CC_REVERB_CUTOFF = 33, CC_REVERB_BALANCE = 34,
+    CC_EARLY_PREDELAY = 50, CC_REVERB_PREDELAY = 52, CC_REVERB_PREFILTER = 53,
+    CC_REVERB_INPUT_DIFFUSION_1 = 54, CC_REVERB_INPUT_DIFFUSION_2 = 55, CC_REVERB_DECAY_DIFFUSION = 56,
     CC_DELAY_TIME = 35, CC_DELAY_FEEDBACK = 36, CC_DELAY_CUTOFF = 37, CC_DELAY_RESONANCE = 38,
     CC_DELAY_BALANCE = 39,
     CC_FILTER_CUTOFF = 41, CC_FILTER_RESONANCE = 42, CC_FILTER_DRIVE = 44,
@@ -564,6 +596,11 @@ enum : uint8_t {
     CC_ENV_AMP_A = 108, CC_ENV_AMP_D = 109, CC_ENV_AMP_S = 110, CC_ENV_AMP_R = 111,
     CC_OSC_1_VOLUME = 114,
 };
+// the controls ReverbFx's handlers take (Fx.h:313-391)
+bool is_reverb_cc(uint8_t c) {
+    return (c >= CC_REVERB_TIME && c <= CC_REVERB_BALANCE) || c == CC_EARLY_PREDELAY ||
+           (c >= CC_REVERB_PREDELAY && c <= CC_REVERB_DECAY_DIFFUSION);
+}
 }  // namespace
 
 int Shadow::control(const olfx_control_event *ev, uint32_t count) {
@@ -573,7 +610,8 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
         uint32_t field;
         float v;
         uint8_t control = ev[k].control;
-        const float topo = kind == OLFX_KIND_FXRACK ? params[(size_t)OLFX_FR_TOPOLOGY * n + ev[k].inst] : 0.f;
+        const float topo = kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK
+                               ? params[(size_t)OLFX_FR_TOPOLOGY * n + ev[k].inst] : 0.f;
         if (topo != 0.f) {
             // No FxRack around these instances (ol_daisy/app/synth/main.cpp:201-207 sends every CC to
             // delay_fx, reverb_fx and filter_fx directly): CC_FILTER_* (41-44) reach a FilterFx's own
@@ -583,7 +621,10 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
             // which only the balance, 34, is audible through the ReverbSc stub), FilterFx 41-44.
             const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
             const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
-            const bool takes = topo == 1.f ? (filter_cc || delay_cc || control == CC_REVERB_BALANCE)
+            // (the plate rack's ReverbFx takes every reverb CC: the table at OLFX_PR_*)
+            const bool reverb_cc = control == CC_REVERB_BALANCE ||
+                                   (kind == OLFX_KIND_PLATERACK && is_reverb_cc(control));
+            const bool takes = topo == 1.f ? (filter_cc || delay_cc || reverb_cc)
                              : topo == 2.f ? delay_cc : topo == 3.f ? control == CC_REVERB_BALANCE : filter_cc;
             if (!takes) continue;
             if (filter_cc) control = (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF);
@@ -779,7 +820,24 @@ extern "C" int olfx_control_map(int kind, uint8_t control, int source, float val
         default: return OLFX_IGNORED;
         }
     }
-    if (kind == OLFX_KIND_FXRACK) {                // FxRack -> FilterFx / DelayFx / ReverbFx
+    if (kind == OLFX_KIND_PLATERACK) {
+        // ReverbFx::UpdateMidiControl / UpdateHardwareControl (Fx.h:313-391) composed with the plate
+        // glue (ReverbFx.cpp:29-37); the rack's other controls below
+        constexpr uint32_t V = OLFX_PR_VERB0;
+        switch (control) {
+        case CC_REVERB_TIME: return put(V + OLFX_DT_DECAY, unit);
+        case CC_REVERB_PREFILTER: return put(V + OLFX_DT_PREFILTER, unit);
+        case CC_REVERB_INPUT_DIFFUSION_1: return put(V + OLFX_DT_INPUT_DIFFUSION1, unit);
+        case CC_REVERB_DECAY_DIFFUSION:
+        case CC_REVERB_INPUT_DIFFUSION_2:          // the reference's quirk (Fx.h:323-324), kept
+            return put(V + OLFX_DT_DECAY_DIFFUSION, unit);
+        case CC_REVERB_CUTOFF: return put(V + OLFX_DT_DAMPING, unit);   // the 0..1 form (Fx.h:328)
+        case CC_REVERB_PREDELAY:
+        case CC_EARLY_PREDELAY: return put(OLFX_FIELD_UPDATE_ONLY, unit);   // members the glue never forwards
+        default: break;
+        }
+    }
+    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK) {   // FxRack -> FilterFx / DelayFx / ReverbFx
         switch (control) {
         case CC_FX_FILTER_CUTOFF: return put(OLFX_FR_FILTER_CUTOFF, midi ? sc(20000.f, 1.f) : sc(20000.f, 1.02f));
         case CC_FX_FILTER_RESONANCE: return put(OLFX_FR_FILTER_RESONANCE, unit);

@@ -271,6 +271,24 @@ struct ChainArgs {
     uint32_t cus;               // compute units of the device (the persistent grid), from olfx_create
 };
 
+// The plate rack (platerack.hip): the rack's delay stage -> dattorro -> balance mix, filter1 and
+// master in one launch.  ring / state / coef are the rack's (FxRackArgs); d carries the plate's rings,
+// state and coefficients (its in / out fields are unused, d.n is n rounded up to 64, d.t0 the
+// plate's own clock).
+struct PlateRackArgs {
+    float *ring;                // [n][kFrMaxDelay][2]
+    uint32_t *state;            // [FRS_N][n]
+    const uint32_t *coef;       // [FRC_N][n]
+    DattorroArgs d;
+    const float *in;            // [2][..][n]
+    float *out;                 // [2][..][n]
+    uint64_t plane;
+    uint32_t n, n_frames;
+    uint32_t t0;                // rack ring position of the first frame: frames since create mod 48000
+    uint32_t cus;               // compute units of the device (the persistent grid)
+};
+hipError_t launch_platerack(const PlateRackArgs &a, hipStream_t s);
+
 hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_chorus(const ChorusArgs &a, hipStream_t s);

@@ -29,6 +29,7 @@ KIND_NAMES = {
     "chain": _lib.KIND_CHAIN,
     "fxrack": _lib.KIND_FXRACK,
     "voice_moog": _lib.KIND_VOICE_MOOG,
+    "platerack": _lib.KIND_PLATERACK,
 }
 
 # parameter field names, in C-ABI order
@@ -49,6 +50,8 @@ PARAMS[_lib.KIND_VOICE_MOOG] = PARAMS[_lib.KIND_VOICE]
 PARAMS[_lib.KIND_CHAIN] = (["chorus_" + p for p in PARAMS[_lib.KIND_CHORUS]]
                            + ["pitch_" + p for p in PARAMS[_lib.KIND_PITCHSHIFT]]
                            + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]])
+# the plate rack: the rack's fields, then the plate's (OLFX_PR_*)
+PARAMS[_lib.KIND_PLATERACK] = PARAMS[_lib.KIND_FXRACK] + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]]
 
 
 def kind_info(kind: int, sample_rate: float = 48000.0) -> _lib.KindInfo:

@@ -37,6 +37,8 @@ RANGES["chain"] = RANGES["chorus"] + RANGES["pitchshift"] + RANGES["dattorro"]
 # random per-instance pre-delay in [0, 1] x 4800 samples (section 8d's gather-path variant)
 RANGES["dattorro_rpd"] = [(0, 1)] + RANGES["dattorro"][1:]
 RANGES["chain_rpd"] = RANGES["chorus"] + RANGES["pitchshift"] + RANGES["dattorro_rpd"]
+# the plate rack: the rack's fields, then the plate's (per-instance pre-delays: its ring is in rows)
+RANGES["platerack"] = RANGES["fxrack"] + RANGES["dattorro_rpd"]
 
 
 def _splitmix64(z: np.ndarray) -> np.ndarray:

@@ -40,6 +40,7 @@ def main():
     # 
     fscale = float(sys.argv[sys.argv.index("--fetch-scale") + 1]) if "--fetch-scale" in sys.argv else 2.0
     base = os.path.join("gpurun_out", f"pmc_{wl}")
+    base = os.environ.get("PMC_DIR", base)      # another directory of passes (tools/platerack_traffic.sh)
     agg, res_k = {}, {}
     for p in sorted(glob.glob(os.path.join(base, "p*"))):
         if not os.path.isdir(p):
