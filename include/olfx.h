@@ -23,6 +23,9 @@
  *   olfx_mix_config / olfx_mix  <- Polyvoice::Process (modules/synthlib/Polyvoice.h:28-33) and
  *                                  VoiceMap::Process (VoiceMap.h:64-73): voices added into one
  *                                  frame, voice by voice
+ *   olfx_sample_bank / olfx_sample_voices <- ol::synth::Sample over its data source and its setters
+ *                                  (modules/synthlib/Sample.h:16-51, Sample.cpp:9-62) behind
+ *                                  SampleSoundSource<1> (SampleSoundSource.h:13-40)
  *   olfx_last_error             <- (reference has none: void returns / NULL, verb.cpp:89-90,227)
  *
  * Audio layout (both host and device pointers accepted, see OLFX_IO_*):
@@ -68,11 +71,18 @@ enum {
                                   (ol_daisy/app/synth/main.cpp:49-52); daisysp::LadderFilter LP24 in place of the
                                   SVF (Filter.h:35-63).  Same OLFX_VC_* parameters (FILTER_DRIVE is ignored:
                                   MoogFilter::SetDrive is a no-op), note events and control changes. */
-    OLFX_KIND_PLATERACK  = 8   /* the effect rack with the Dattorro plate as its reverb stage: DelayFx<2> ->
+    OLFX_KIND_PLATERACK  = 8,  /* the effect rack with the Dattorro plate as its reverb stage: DelayFx<2> ->
                                   Dattorro((a0 + a1) / 2) mixed by REVERB_BALANCE -> FilterFx<2> -> master, one
                                   launch (platerack.hip).  The stage the reference's rack was written for: its
                                   ol::fx::Reverb interface (Reverb.h:44-65) is the DattorroVerb_set* list and
                                   ReverbFx.cpp:11-37 still holds the glue, commented out.  OLFX_PR_* fields. */
+    /* 9 stays unassigned: tests/test_platerack_host.py pins it as "a kind nobody has" (OLFX_E_KIND) */
+    OLFX_KIND_VOICE_SAMPLE = 10 /* SynthVoice(SampleSoundSource<1>(Sample), SvfFilter): sample playback from a
+                                  device-resident bank (olfx_sample_bank / olfx_sample_voices) -> SVF LP -> amp
+                                  env; mono out, no input.  OLFX_VC_* parameters, note events, control changes,
+                                  olfx_set_member, olfx_update and the voice buses as OLFX_KIND_VOICE.  GateOn /
+                                  NoteOn also Seek(0) and Play() the sample, GateOff / NoteOff Pause() it
+                                  (SampleSoundSource.h:21-26); SetFreq only stores the pitch (:28-30). */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -324,6 +334,39 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
 int olfx_mix_config(olfx_engine *e, uint32_t n_buses, const uint32_t *offsets, const uint32_t *order);
 int olfx_mix(olfx_engine *e, const float *voice_out, float *bus_out, uint32_t n_frames, int io_flags,
              void *stream);
+
+/* ---- sample voices (OLFX_KIND_VOICE_SAMPLE): ol::synth::Sample over a device-resident bank ----
+   The bank is n_samples mono float32 buffers: sample k is pcm[offsets[k] .. offsets[k+1]) (frames; offsets
+   has n_samples + 1 entries, starts at 0 and never decreases; each sample has fewer than 2^32 - 1 frames).
+   olfx_sample_bank copies the host arrays to the device and replaces the whole bank; it waits for this
+   engine's queued work only (as olfx_reset).  After it every voice's Sample is fresh (not playing, cursor 0);
+   a voice keeps its assignment if the index is still valid, else it becomes unassigned.  n_samples = 0
+   removes the bank.  OLFX_E_NOMEM (allocation failed) leaves the old bank in place.
+   The data source is the in-memory one: Read writes pcm[pos++] and returns 1 while pos < len, else writes
+   nothing and returns 0; Seek(k) sets pos = min(k, len).  The frame handed to Sample::Process is the
+   caller's zeroed frame (0.0f), as with olfx_mix: a paused, unassigned or exhausted voice feeds zeros into
+   its filter.  Sample::Process's loop rule is the reference's (Sample.cpp:13-20): in Loop mode,
+   Seek(loop_start) when nothing was read or when loop_end != 0 and the frame count passed loop_end; loop
+   points may be any value (an end past the sample gives one silent tick per turn, a start past it silence
+   after the first pass).  OneShot at the end keeps `playing` and reads nothing.
+   olfx_sample_voices gives voices their Sample: validated first (a rejected call changes nothing), applied
+   at the next block boundary, before that boundary's note events.  A new `sample` index, or OLFX_NO_SAMPLE,
+   constructs a fresh Sample (OneShot unless the record says Loop, not playing, cursor 0); the same index
+   with a new mode or loop points is SetPlayMode / SetLoopStart / SetLoopEnd: no seek, the cursor is kept.
+   olfx_reset keeps the bank and the assignments, as it keeps the olfx_mix_config buses (configuration, not
+   state); every Sample is fresh after it. */
+#define OLFX_NO_SAMPLE 0xFFFFFFFFu
+enum { OLFX_SAMPLE_ONESHOT = 0, OLFX_SAMPLE_LOOP = 1 };   /* ol::synth::SamplePlayMode (Sample.h:11-14) */
+typedef struct olfx_sample_voice {
+    uint32_t inst;          /* voice */
+    uint32_t sample;        /* index into the bank, or OLFX_NO_SAMPLE */
+    uint32_t play_mode;     /* OLFX_SAMPLE_* */
+    uint32_t pad;
+    uint64_t loop_start;    /* frames */
+    uint64_t loop_end;      /* frames; 0 = none */
+} olfx_sample_voice;
+int olfx_sample_bank(olfx_engine *e, uint32_t n_samples, const uint64_t *offsets, const float *pcm);
+int olfx_sample_voices(olfx_engine *e, const olfx_sample_voice *recs, uint32_t n);
 
 /* Block until all work queued by this engine is done (engine-scoped, see olfx_reset). */
 int olfx_sync(olfx_engine *e);

@@ -253,6 +253,10 @@ public:
         check(olfx_mix(e_, voice_out, bus_out, n_frames, io, stream), e_, "olfx_mix");
     }
 
+protected:
+    VoiceBank(int kind, uint32_t n_inst, float sample_rate, uint32_t block, int device)
+        : Engine(kind, n_inst, sample_rate, block, device) {}
+
 private:
     /* the engine queues note events itself and applies them, in call order, at the next process
        (olfx_note_events), so Engine::process (BlockAdapter) sees them too */
@@ -260,6 +264,46 @@ private:
         olfx_event ev{};
         ev.inst = i; ev.type = type; ev.note = note; ev.velocity = vel;
         check(olfx_note_events(e_, &ev, 1), e_, "olfx_note_events");
+    }
+};
+
+/* SynthVoice(new SampleSoundSource<1>(sample), new SvfFilter, ...) over N voices (OLFX_KIND_VOICE_SAMPLE):
+   the reference's drum machine (VoiceMap over sample voices, workouts/attic/drum_main.cpp:53-72).
+   VoiceBank's methods (UpdateConfig, NoteOn / NoteOff, Process, the buses) plus the bank and each
+   voice's ol::synth::Sample (Sample.h:16-51).  NoteOn / GateOn also Seek(0) and Play() the sample,
+   NoteOff / GateOff Pause() it; all of it lands at the next block boundary. */
+class SamplerBank : public VoiceBank {
+public:
+    enum class PlayMode : uint32_t { OneShot = OLFX_SAMPLE_ONESHOT, Loop = OLFX_SAMPLE_LOOP };
+    SamplerBank(uint32_t n_inst, float sample_rate, uint32_t block = 256, int device = 0)
+        : VoiceBank(OLFX_KIND_VOICE_SAMPLE, n_inst, sample_rate, block, device) {}
+    /* Replace the bank with these mono buffers (copied to the device).  Every voice's Sample is fresh
+       afterwards; a voice whose index the new bank lacks becomes unassigned. */
+    void SetBank(const std::vector<std::vector<float>> &samples) {
+        std::vector<uint64_t> off(1, 0);
+        std::vector<float> pcm;
+        for (const auto &s : samples) {
+            pcm.insert(pcm.end(), s.begin(), s.end());
+            off.push_back(pcm.size());
+        }
+        if (pcm.empty()) pcm.push_back(0.f);
+        check(olfx_sample_bank(e_, (uint32_t)samples.size(), off.data(), pcm.data()), e_, "olfx_sample_bank");
+    }
+    /* new Sample(bank[sample]) for voice i (OLFX_NO_SAMPLE: none); the same index again is
+       SetPlayMode / SetLoopStart / SetLoopEnd on the Sample it has (no seek) */
+    void SetSample(uint32_t i, uint32_t sample, PlayMode mode = PlayMode::OneShot, uint64_t loop_start = 0,
+                   uint64_t loop_end = 0) {
+        const olfx_sample_voice r{i, sample, (uint32_t)mode, 0u, loop_start, loop_end};
+        check(olfx_sample_voices(e_, &r, 1), e_, "olfx_sample_voices");
+    }
+    void GateOn(uint32_t i) { gate(i, OLFX_EV_GATE_ON); }
+    void GateOff(uint32_t i) { gate(i, OLFX_EV_GATE_OFF); }
+
+private:
+    void gate(uint32_t i, uint8_t type) {
+        olfx_voice_event ev{};
+        ev.inst = i; ev.type = type;
+        check(olfx_voice_events(e_, &ev, 1), e_, "olfx_voice_events");
     }
 };
 

@@ -31,6 +31,11 @@ KIND_CHAIN = 5
 KIND_FXRACK = 6
 KIND_VOICE_MOOG = 7
 KIND_PLATERACK = 8
+KIND_VOICE_SAMPLE = 10      # 9 is unassigned (olfx.h)
+
+NO_SAMPLE = 0xFFFFFFFF
+SAMPLE_ONESHOT = 0
+SAMPLE_LOOP = 1
 
 IO_DEVICE = 0
 IO_HOST = 1
@@ -89,6 +94,17 @@ class ControlEvent(ctypes.Structure):
     ]
 
 
+class SampleVoice(ctypes.Structure):
+    _fields_ = [
+        ("inst", ctypes.c_uint32),
+        ("sample", ctypes.c_uint32),
+        ("play_mode", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+        ("loop_start", ctypes.c_uint64),
+        ("loop_end", ctypes.c_uint64),
+    ]
+
+
 CTL_MIDI = 0
 CTL_HARDWARE = 1
 IGNORED = 1
@@ -128,6 +144,8 @@ SIGNATURES = {
     "olfx_mix_config": (ctypes.c_int, [_P, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "olfx_mix": (ctypes.c_int, [_P, _P, _P, _U32, ctypes.c_int, _P]),
     "olfx_num_buses": (_U32, [_P]),
+    "olfx_sample_bank": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_F)]),
+    "olfx_sample_voices": (ctypes.c_int, [_P, ctypes.POINTER(SampleVoice), _U32]),
     # include/olfx_sample.h: per-instance, per-sample operators (one block of latency)
     "olfx_sample_pool_config": (ctypes.c_int, [ctypes.c_int, _U32]),
     "olfx_sample_pool_config_depth": (ctypes.c_int, [ctypes.c_int, _U32, _U32]),

@@ -132,6 +132,11 @@ struct olfx_engine {
 
     // voice
     float *vc_state = nullptr, *vc_coef = nullptr;
+    // sample voices: each voice's Sample ([SMC_N][n], in d_mem) and the bank (an allocation of its own:
+    // configuration, kept by olfx_reset)
+    uint32_t *sm_asg = nullptr;
+    float *sm_bank = nullptr;
+    uint64_t sm_bank_bytes = 0;
     // voice buses (olfx_mix_config): [n_buses + 1] offsets, then the voice lists
     uint32_t *mix_dev = nullptr;
     uint32_t mix_quad = 0;                  // contiguous buses on multiples of 4 voices (voice_mix_v4)
@@ -207,6 +212,7 @@ size_t carve(olfx_engine *e, char *base) {
         take(e->vc_state, (size_t)voice_state_slots(kind) * n * 4);
         take(e->vc_coef, (size_t)VCC_N * n * 4);
     }
+    if (kind == OLFX_KIND_VOICE_SAMPLE) take(e->sm_asg, (size_t)SMC_N * n * 4);
     return off;
 }
 
@@ -234,6 +240,7 @@ uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
         break;
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: dst[0] = e->vc_coef; break;
+    case OLFX_KIND_VOICE_SAMPLE: dst[0] = e->vc_coef; dst[1] = e->sm_asg; break;
     default: break;
     }
     a->nseg = sg.nseg;
@@ -514,7 +521,8 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_chorus(ch_args(e->ch_pring, e->ch_cring, e->ch_state, e->ch_coef, din, dout, 1), s);
         break;
     case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG: {
+    case OLFX_KIND_VOICE_MOOG:
+    case OLFX_KIND_VOICE_SAMPLE: {
         VoiceArgs a{};
         a.state = e->vc_state;
         a.coef = e->vc_coef;
@@ -524,7 +532,10 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.moog = e->kind == OLFX_KIND_VOICE_MOOG;
         a.ev_more = ev.ev_more;
         a.ev = ev.ev;
-        r = launch_voice(a, s);
+        a.smp = e->sm_asg;
+        a.bank = e->sm_bank;
+        a.bank_bytes = (uint32_t)e->sm_bank_bytes;
+        r = e->kind == OLFX_KIND_VOICE_SAMPLE ? launch_sampler(a, s) : launch_voice(a, s);
         break;
     }
     case OLFX_KIND_FXRACK: {
@@ -766,6 +777,7 @@ int olfx_destroy(olfx_engine *e) {
     if (e->d_in) (void)hipFree(e->d_in);
     if (e->d_out) (void)hipFree(e->d_out);
     if (e->mix_dev) (void)hipFree(e->mix_dev);
+    if (e->sm_bank) (void)hipFree(e->sm_bank);
     if (e->mix_done) (void)hipEventDestroy(e->mix_done);
     if (e->switched) (void)hipEventDestroy(e->switched);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -970,6 +982,49 @@ int olfx_mix(olfx_engine *e, const float *voice_out, float *bus_out, uint32_t n_
     return OLFX_OK;
 }
 
+// ---- sample voices: the bank and each voice's Sample (validation and layout: host::Shadow) ----
+int olfx_sample_bank(olfx_engine *e, uint32_t n_samples, const uint64_t *offsets, const float *pcm) {
+    if (!e) return OLFX_E_ARG;
+    host::BankPlan plan;
+    if (const int rc = e->report(e->hs.bank_plan(n_samples, offsets, pcm, &plan))) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    // the new bank first: a failed allocation leaves the current one in place
+    float *fresh = nullptr;
+    if (plan.floats) {
+        std::vector<float> h;
+        try {
+            h.assign((size_t)plan.floats, 0.f);        // aligned starts, zeroed gaps and tail
+        } catch (const std::bad_alloc &) {
+            return e->fail(OLFX_E_NOMEM, "olfx_sample_bank: host staging of %llu bytes", (unsigned long long)plan.floats * 4);
+        }
+        for (size_t k = 0; k < plan.len.size(); ++k)
+            if (plan.len[k]) std::memcpy(h.data() + plan.base[k], pcm + offsets[k], (size_t)plan.len[k] * 4);
+        hipError_t r = hipMalloc((void **)&fresh, (size_t)plan.floats * 4);
+        if (r != hipSuccess)
+            return e->fail(OLFX_E_NOMEM, "olfx_sample_bank: hipMalloc(%llu bytes): %s", (unsigned long long)plan.floats * 4,
+                           hipGetErrorString(r));
+        r = hipMemcpy(fresh, h.data(), (size_t)plan.floats * 4, hipMemcpyHostToDevice);
+        if (r != hipSuccess) {
+            (void)hipFree(fresh);
+            return e->hip_fail(r, "olfx_sample_bank upload");
+        }
+    }
+    // the blocks queued so far still read the old bank: this engine's work only, as olfx_reset
+    if (const int rc = wait_engine(e)) {
+        if (fresh) (void)hipFree(fresh);
+        return rc;
+    }
+    if (e->sm_bank) (void)hipFree(e->sm_bank);
+    e->sm_bank = fresh;
+    e->sm_bank_bytes = plan.floats * 4;
+    e->hs.bank_commit(std::move(plan));
+    return OLFX_OK;
+}
+
+int olfx_sample_voices(olfx_engine *e, const olfx_sample_voice *recs, uint32_t n) {
+    return e ? e->report(e->hs.sample_voices(recs, n)) : OLFX_E_ARG;
+}
+
 int olfx_sync(olfx_engine *e) {
     if (!e) return OLFX_E_ARG;
     HIPCHK(e, hipSetDevice(e->device));
@@ -999,6 +1054,7 @@ const char *olfx_kernel_name(const olfx_engine *e) {
     case OLFX_KIND_PITCHSHIFT: return "chorus_block_v11";
     case OLFX_KIND_VOICE: return "voice_block_v5";
     case OLFX_KIND_VOICE_MOOG: return "voice_block_v4";
+    case OLFX_KIND_VOICE_SAMPLE: return "sampler_block_v1";
     case OLFX_KIND_CHAIN: return "chain_block_v5";
     case OLFX_KIND_FXRACK: return "fxrack_block_v3";
     case OLFX_KIND_PLATERACK: return "platerack_block_v1";

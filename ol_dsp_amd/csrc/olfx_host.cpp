@@ -51,7 +51,8 @@ uint32_t n_params_of(int kind) {
     case OLFX_KIND_CHORUS: return OLFX_CH_NPARAMS;
     case OLFX_KIND_PITCHSHIFT: return OLFX_PS_NPARAMS;
     case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG: return OLFX_VC_NPARAMS;
+    case OLFX_KIND_VOICE_MOOG:
+    case OLFX_KIND_VOICE_SAMPLE: return OLFX_VC_NPARAMS;
     case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
     case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
     case OLFX_KIND_PLATERACK: return OLFX_PR_NPARAMS;
@@ -102,6 +103,7 @@ void default_params(int kind, float *p) {
         break;
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG:
+    case OLFX_KIND_VOICE_SAMPLE:
         // SynthVoice member defaults (SynthVoice.h:285-311); Config order (Voice.h:14-31)
         p[OLFX_VC_FILTER_CUTOFF] = 0.0f;
         p[OLFX_VC_FILTER_RESONANCE] = 0.0f;
@@ -175,6 +177,7 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
     case OLFX_KIND_PITCHSHIFT: return ch * n;
     case OLFX_KIND_VOICE: return vc * n;
     case OLFX_KIND_VOICE_MOOG: return vc * n + (uint64_t)(VCS_N_MOOG - VCS_N) * 4 * n;
+    case OLFX_KIND_VOICE_SAMPLE: return (vc + (uint64_t)SMC_N * 4) * n;   // the bank is the caller's data, not state
     case OLFX_KIND_CHAIN: return (dt + 2 * ch) * n;
     case OLFX_KIND_FXRACK: return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n;
     case OLFX_KIND_PLATERACK:       // the rack's ring + the plate's, the plate's instances padded to 64
@@ -191,6 +194,7 @@ double algorithmic_bytes_per_frame(int kind) {
     case OLFX_KIND_PITCHSHIFT: return 40.0;    // 2 x (w + 2 taps) x 4 + 16 I/O
     case OLFX_KIND_VOICE: return 5.4;          // 4 B out + per-block state
     case OLFX_KIND_VOICE_MOOG: return 5.7;     // 4 B out + per-block state (9 more state words)
+    case OLFX_KIND_VOICE_SAMPLE: return 8.0;   // 4 B of the sample read + 4 B out
     case OLFX_KIND_CHAIN: return 228.6;
     case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
     case OLFX_KIND_PLATERACK: return 32.0 + 164.6 - 16.0;   // rack + plate - the plate's own I/O (in LDS now)
@@ -207,6 +211,7 @@ double algorithmic_read_bytes_per_frame(int kind) {
     case OLFX_KIND_PITCHSHIFT: return 24.0;    // 2 x 2 taps x 4 + 8 in
     case OLFX_KIND_VOICE: return 0.7;          // per-block state and coefficients
     case OLFX_KIND_VOICE_MOOG: return 0.85;
+    case OLFX_KIND_VOICE_SAMPLE: return 4.0;   // the sample
     case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
     case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
     case OLFX_KIND_PLATERACK: return 16.0 + 6445.0 * 4.0 / 256.0;   // rack + the plate's taps (its input is in LDS)
@@ -415,6 +420,7 @@ Segments coef_segments(int kind) {
     case OLFX_KIND_PLATERACK: return {2, {FRC_N, DTC_N, 0}};       // rack, plate
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
+    case OLFX_KIND_VOICE_SAMPLE: return {2, {VCC_N, SMC_N, 0}};   // the voice, its Sample
     default: return {0, {0, 0, 0}};
     }
 }
@@ -445,8 +451,10 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
         break;
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG:
+    case OLFX_KIND_VOICE_SAMPLE:
         derive_voice(p, configured[i] != 0, kind == OLFX_KIND_VOICE_MOOG, sr, fc);
         std::memcpy(w, fc, VCC_N * 4);
+        if (kind == OLFX_KIND_VOICE_SAMPLE) sample_record(i, w + VCC_N);
         break;
     default: break;
     }
@@ -573,6 +581,74 @@ int Shadow::update(uint32_t first, uint32_t count) {
     return OLFX_OK;
 }
 
+// ---- sample voices ----
+int Shadow::bank_plan(uint32_t n_samples, const uint64_t *offsets, const float *pcm, BankPlan *plan) {
+    if (kind != OLFX_KIND_VOICE_SAMPLE) return fail(OLFX_E_STATE, "olfx_sample_bank: not a sample-voice engine");
+    plan->base.clear();
+    plan->len.clear();
+    plan->floats = 0;
+    if (!n_samples) return OLFX_OK;
+    if (!offsets || offsets[0] != 0) return fail(OLFX_E_ARG, "olfx_sample_bank: offsets must start at 0");
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n_samples; ++k) {
+        if (offsets[k + 1] < offsets[k]) return fail(OLFX_E_ARG, "olfx_sample_bank: offsets decrease at sample %u", k);
+        const uint64_t len = offsets[k + 1] - offsets[k];
+        if (len >= 0xFFFFFFFFull) return fail(OLFX_E_ARG, "olfx_sample_bank: sample %u has 2^32 - 1 frames or more", k);
+        if (at + len > kSmMaxBankFloats) return fail(OLFX_E_ARG, "olfx_sample_bank: the bank exceeds %llu frames",
+                                                     (unsigned long long)kSmMaxBankFloats);
+        plan->base.push_back((uint32_t)at);
+        plan->len.push_back((uint32_t)len);
+        at = (at + len + kSmAlign - 1) / kSmAlign * kSmAlign;
+    }
+    if (offsets[n_samples] && !pcm) return fail(OLFX_E_ARG, "olfx_sample_bank: null pcm");
+    plan->floats = at + kSmAlign;           // the padded tail: a fetch that starts inside a sample ends inside the bank
+    return OLFX_OK;
+}
+
+void Shadow::bank_commit(BankPlan &&plan) {
+    bank = std::move(plan);
+    for (SampleAsg &a : samples) {
+        if (a.sample != OLFX_NO_SAMPLE && a.sample >= bank.len.size()) a = SampleAsg{OLFX_NO_SAMPLE, 0, 0, 0, a.gen};
+        ++a.gen;                            // a fresh Sample over the new data
+    }
+    mark_dirty(0, n);
+}
+
+int Shadow::sample_voices(const olfx_sample_voice *recs, uint32_t count) {
+    if (kind != OLFX_KIND_VOICE_SAMPLE) return fail(OLFX_E_STATE, "olfx_sample_voices: not a sample-voice engine");
+    if (count && !recs) return fail(OLFX_E_ARG, "olfx_sample_voices: null records");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (recs[k].inst >= n) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: voice out of range", k);
+        if (recs[k].sample != OLFX_NO_SAMPLE && recs[k].sample >= bank.len.size())
+            return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: sample %u of %zu", k, recs[k].sample, bank.len.size());
+        if (recs[k].play_mode > OLFX_SAMPLE_LOOP) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: bad play mode", k);
+    }
+    for (uint32_t k = 0; k < count; ++k) {
+        SampleAsg &a = samples[recs[k].inst];
+        if (a.sample != recs[k].sample) ++a.gen;       // another sample (or none): a new Sample object
+        a.sample = recs[k].sample;
+        a.mode = recs[k].play_mode;
+        a.loop_start = recs[k].loop_start;
+        a.loop_end = recs[k].loop_end;
+        mark_dirty(recs[k].inst, 1);
+    }
+    return OLFX_OK;
+}
+
+// The Sample's members reduced to what Sample::Process can observe over a len-frame source: Seek(k)
+// puts the data cursor at min(k, len), and the frame count is compared with loop_end only after a
+// read, where it equals the data cursor (<= len): a loop_end >= len never fires, like 0.
+void Shadow::sample_record(uint32_t i, uint32_t *w) const {
+    const SampleAsg &a = samples[i];
+    const bool has = a.sample != OLFX_NO_SAMPLE && a.sample < bank.len.size();
+    const uint32_t len = has ? bank.len[a.sample] : 0u;
+    w[SMC_BASE] = has ? bank.base[a.sample] : 0u;
+    w[SMC_LEN] = len;
+    w[SMC_LS] = (uint32_t)std::min<uint64_t>(a.loop_start, len);
+    w[SMC_LE] = a.loop_end < len ? (uint32_t)a.loop_end : 0u;
+    w[SMC_MODE] = (a.mode == OLFX_SAMPLE_LOOP ? 1u : 0u) | a.gen << 1;
+}
+
 bool Shadow::uniform_predelay() const {
     const float *pd = params.data() + (size_t)OLFX_DT_PREDELAY * n;
     const uint32_t d0 = dattorro_predelay_samples(pd[0]);
@@ -689,7 +765,11 @@ float mtof_note(uint8_t note) {
 // envelopes (:245-251); NoteOff / GateOff = gate off (:236-239, :253-256); GateOn = gate on
 // (:231-234); SetFrequency = freq_ (:264-267).  The last gate call decides the gate, any NoteOn
 // retriggers (gate calls do not touch the envelope modes), the last NoteOn / SetFrequency the pitch.
+// Sample voices: SynthVoice::GateOn / GateOff also reach the sound source (SynthVoice.h:231-239), where
+// GateOn = Seek(0) + Play() and GateOff = Pause() (SampleSoundSource.h:21-26): any NoteOn / GateOn of
+// the block seeks to 0 (VEV_SEEK), and `playing` follows the last gate call like the gate itself.
 void Shadow::fold_events() {
+    const uint32_t seek = kind == OLFX_KIND_VOICE_SAMPLE ? (uint32_t)VEV_SEEK : 0u;
     folded.clear();
     for (const olfx_voice_event &ev : events) {
         int32_t &k = ev_slot[ev.inst];
@@ -700,12 +780,12 @@ void Shadow::fold_events() {
         Folded &r = folded[(size_t)k];
         switch (ev.type) {
         case OLFX_EV_NOTE_ON: {
-            r.op |= VEV_GATE_SET | VEV_GATE_ON | VEV_RETRIGGER | VEV_FREQ;
+            r.op |= VEV_GATE_SET | VEV_GATE_ON | VEV_RETRIGGER | VEV_FREQ | seek;
             const float hz = mtof_note(ev.note);                              // daisysp::mtof
             std::memcpy(&r.freq, &hz, 4);
             break;
         }
-        case OLFX_EV_GATE_ON: r.op |= VEV_GATE_SET | VEV_GATE_ON; break;
+        case OLFX_EV_GATE_ON: r.op |= VEV_GATE_SET | VEV_GATE_ON | seek; break;
         case OLFX_EV_SET_FREQUENCY:
             r.op |= VEV_FREQ;
             std::memcpy(&r.freq, &ev.value, 4);

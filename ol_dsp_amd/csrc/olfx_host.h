@@ -58,6 +58,19 @@ size_t max_packet_words(int kind, uint32_t n);
 
 struct Folded { uint32_t inst, op, freq, pad; };
 
+// ---- sample voices: the bank's layout and each voice's Sample (olfx_sample_bank / olfx_sample_voices) ----
+// A validated bank: where each sample goes in the device allocation (kSmAlign-aligned starts, a
+// padded tail) and its frames.  n_samples = 0: no bank (floats = 0).
+struct BankPlan {
+    std::vector<uint32_t> base, len;      // [n_samples], floats / frames
+    uint64_t floats = 0;                  // the allocation, padding included
+};
+struct SampleAsg {
+    uint32_t sample = OLFX_NO_SAMPLE, mode = OLFX_SAMPLE_ONESHOT;
+    uint64_t loop_start = 0, loop_end = 0;
+    uint32_t gen = 1;                     // bumped whenever the voice gets a fresh Sample object
+};
+
 // The host shadow of an engine: what the caller has set, what of it the device has yet to see, and
 // the note events queued for the next block.  Every operation that can refuse returns OLFX_OK or
 // an OLFX_E_* code with the reason in `msg`, and a refused call changes nothing.
@@ -79,9 +92,16 @@ struct Shadow {
     uint32_t n_more = 0;                  // overflow records
     std::vector<int32_t> ev_slot;         // voice -> its record in `folded` during fold_events, else -1
     std::vector<uint32_t> h_words;        // scratch for a record
+    // sample voices: the bank in use and every voice's Sample.  Configuration like the voice buses:
+    // reset() keeps both (and makes every Sample fresh)
+    BankPlan bank;
+    std::vector<SampleAsg> samples;       // [n]
     char msg[160] = "";
 
-    void init(int kind_, uint32_t n_, float sr_) { kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_); }
+    void init(int kind_, uint32_t n_, float sr_) {
+        kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_);
+        samples.assign(kind_ == OLFX_KIND_VOICE_SAMPLE ? n_ : 0u, SampleAsg{});
+    }
     // Every instance at the reference's defaults, unconfigured, all dirty; nothing queued.
     void reset();
 
@@ -93,6 +113,14 @@ struct Shadow {
     int note_events(const olfx_event *ev, uint32_t count);
     int voice_events(const olfx_voice_event *ev, uint32_t count);
     bool uniform_predelay() const;        // reverb: every instance has the same pre-delay in samples
+    // olfx_sample_bank in two steps, so that the engine can allocate and copy in between: the layout of
+    // a valid bank (nothing changes), then the switch to it (every Sample fresh; assignments whose index
+    // the new bank lacks become unassigned)
+    int bank_plan(uint32_t n_samples, const uint64_t *offsets, const float *pcm, BankPlan *plan);
+    void bank_commit(BankPlan &&plan);
+    int sample_voices(const olfx_sample_voice *recs, uint32_t count);
+    // voice i's Sample as the kernel reads it (SMC_* words)
+    void sample_record(uint32_t i, uint32_t *w) const;
 
     // The coefficient record of instance i from its current parameters, in coef_segments' order.
     void derive_record(uint32_t i, uint32_t *w) const;

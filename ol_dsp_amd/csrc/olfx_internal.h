@@ -225,6 +225,10 @@ struct VoiceArgs {
     // this block's events (nullptr: none), at most one record per voice (kVevCap above)
     const uint2 *ev;            // [n_groups][kVevCap] fixed slots, n_groups = ceil(n / 64)
     const uint2 *ev_more;       // overflow list
+    // sample voices (sampler.hip): each voice's Sample and the bank it plays from
+    const uint32_t *smp;        // [SMC_N][n]
+    const float *bank;          // bank_bytes bytes (nullptr / 0: no bank -- every SMC_LEN is 0 then)
+    uint32_t bank_bytes;
 };
 
 // Coefficient records of the instances whose parameters changed (olfx_engine.cpp submit_control):
@@ -293,6 +297,7 @@ hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_chorus(const ChorusArgs &a, hipStream_t s);
 hipError_t launch_voice(const VoiceArgs &a, hipStream_t s);
+hipError_t launch_sampler(const VoiceArgs &a, hipStream_t s);
 
 // ----------------------------------------------------------------------------------------------
 // Voice buses (mix.hip): the Polyvoice / VoiceMap sums.  Bus b of frame f = out[f][b] plus the

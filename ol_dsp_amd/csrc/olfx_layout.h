@@ -112,7 +112,9 @@ enum {
     VCS_LZ0 = VCS_N, VCS_LZ1 = VCS_LZ0 + 4, VCS_LOLD = VCS_LZ1 + 4,
     VCS_N_MOOG
 };
-inline bool is_voice_kind(int k) { return k == OLFX_KIND_VOICE || k == OLFX_KIND_VOICE_MOOG; }
+inline bool is_voice_kind(int k) {
+    return k == OLFX_KIND_VOICE || k == OLFX_KIND_VOICE_MOOG || k == OLFX_KIND_VOICE_SAMPLE;
+}
 inline uint32_t voice_state_slots(int k) { return k == OLFX_KIND_VOICE_MOOG ? (uint32_t)VCS_N_MOOG : (uint32_t)VCS_N; }
 
 // Note events of one block, folded per voice on the host (olfx_host.cpp fold_events) and applied
@@ -124,6 +126,7 @@ enum : uint32_t {
     VEV_GATE_ON = 2u,
     VEV_RETRIGGER = 4u,         // Adsr::Retrigger(true) on both envelopes: mode ATTACK, x = 0
     VEV_FREQ = 8u,              // freq_ := the record's frequency (mtof(note) for NoteOn, SetFrequency's Hz)
+    VEV_SEEK = 0x10u,           // sample voices: Seek(0) (SampleSoundSource::GateOn, any NoteOn / GateOn of the block)
     VEV_MORE = 0x80u,           // (slot 0 of a crowded workgroup) its records are in the overflow list
 };
 // Event records, 8 B: x = (voice & 63) | VEV_* ops << 8, y = frequency bits; x = 0 is an empty slot.
@@ -132,6 +135,27 @@ enum : uint32_t {
 // kVevCap records puts them all in the overflow list and marks slot 0:
 // x = VEV_MORE << 8 | count << 16, y = first record in ev_more (a second round trip, for it only).
 constexpr uint32_t kVevCap = 4;
+
+// ----------------------------------------------------------------------------------------------
+// Sample voices (sampler.hip): SynthVoice(SampleSoundSource<1>(Sample), SvfFilter).  The voice's
+// coefficients and state are the Svf voice's; the oscillator's two state words hold the Sample.
+// The bank is one device allocation: sample k starts at a multiple of kSmAlign floats and the
+// allocation ends with kSmAlign floats of padding (zeros), so a 64-lane fetch that starts inside a
+// sample stays inside the allocation.
+// ----------------------------------------------------------------------------------------------
+constexpr uint32_t kSmAlign = 64;           // floats: the fetch width (one voice's 256 contiguous bytes)
+constexpr uint64_t kSmMaxBankFloats = (1ull << 30) - 2 * kSmAlign;   // 32-bit byte offsets into the bank
+// A voice's Sample over the bank ([SMC_N][n] words, delivered like the coefficients).
+enum {
+    SMC_BASE = 0,       // the sample's first frame in the bank, in floats (0 when unassigned)
+    SMC_LEN,            // its frames (0: unassigned -- nothing is ever read)
+    SMC_LS,             // min(loop_start, len): where Seek(loop_start) puts the data cursor
+    SMC_LE,             // loop_end where it can fire (0 < loop_end < len), else 0
+    SMC_MODE,           // bit 0: Loop; bits 1..: the generation of this Sample object (a new one = a fresh Sample)
+    SMC_N
+};
+// state words (the oscillator's, unused here): the data cursor; bit 0 playing, bits 1.. the generation seen
+enum { VCS_SM_POS = VCS_PHASE, VCS_SM_FLAGS = VCS_PORT_Z };
 
 // ----------------------------------------------------------------------------------------------
 // Effect rack ol::fx::FxRack<2> (fxrack.hip): delay lines + two Svf (channel 0) + ReverbSc stub.

@@ -30,6 +30,7 @@ KIND_NAMES = {
     "fxrack": _lib.KIND_FXRACK,
     "voice_moog": _lib.KIND_VOICE_MOOG,
     "platerack": _lib.KIND_PLATERACK,
+    "voice_sample": _lib.KIND_VOICE_SAMPLE,
 }
 
 # parameter field names, in C-ABI order
@@ -47,6 +48,7 @@ PARAMS = {
                        "master_volume", "topology"],
 }
 PARAMS[_lib.KIND_VOICE_MOOG] = PARAMS[_lib.KIND_VOICE]
+PARAMS[_lib.KIND_VOICE_SAMPLE] = PARAMS[_lib.KIND_VOICE]
 PARAMS[_lib.KIND_CHAIN] = (["chorus_" + p for p in PARAMS[_lib.KIND_CHORUS]]
                            + ["pitch_" + p for p in PARAMS[_lib.KIND_PITCHSHIFT]]
                            + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]])
@@ -295,6 +297,37 @@ class Engine:
         check(self.lib.olfx_mix(self._h, ctypes.c_void_p(v.ctypes.data), ctypes.c_void_p(bus_out.ctypes.data),
                                 frames, _lib.IO_HOST, ctypes.c_void_p(stream)), self._h)
         return bus_out
+
+    # ---- sample voices: ol::synth::Sample over a device-resident bank (Sample.cpp:9-62) ----
+    def sample_bank(self, samples: Sequence) -> None:
+        """Replace the bank: `samples` is a list of mono float32 arrays (copied to the device); []
+        removes it.  Every voice's Sample is fresh afterwards; assignments whose index the new bank
+        lacks become unassigned (olfx_sample_bank)."""
+        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).ravel()) for a in samples]
+        off = np.zeros(len(arrs) + 1, np.uint64)
+        if arrs:
+            off[1:] = np.cumsum([len(a) for a in arrs])
+        pcm = np.ascontiguousarray(np.concatenate(arrs) if arrs and off[-1] else np.zeros(1, np.float32))
+        check(self.lib.olfx_sample_bank(self._h, len(arrs), off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                        pcm.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._h)
+
+    def sample_voices(self, records: Iterable[Sequence]) -> None:
+        """Give voices their Sample at the next block boundary: iterable of (inst, sample[, play_mode[,
+        loop_start[, loop_end]]]); sample None or _lib.NO_SAMPLE unassigns, play_mode 0 OneShot /
+        1 Loop (or "oneshot" / "loop").  A new sample index is a fresh Sample; the same index with other
+        loop settings keeps the cursor (olfx_sample_voices)."""
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.SampleVoice * len(recs))()
+        for k, r in enumerate(recs):
+            arr[k].inst = int(r[0])
+            arr[k].sample = _lib.NO_SAMPLE if r[1] is None else int(r[1])
+            mode = r[2] if len(r) > 2 else 0
+            arr[k].play_mode = {"oneshot": 0, "loop": 1}.get(mode, mode) if isinstance(mode, str) else int(mode)
+            arr[k].loop_start = int(r[3]) if len(r) > 3 else 0
+            arr[k].loop_end = int(r[4]) if len(r) > 4 else 0
+        check(self.lib.olfx_sample_voices(self._h, arr, len(recs)), self._h)
 
     def sync(self) -> None:
         check(self.lib.olfx_sync(self._h), self._h)

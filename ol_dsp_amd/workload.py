@@ -33,6 +33,7 @@ RANGES = {
                (0, 1), "int5", (0, 1), 0.0],
 }
 RANGES["voice_moog"] = RANGES["voice"]
+RANGES["voice_sample"] = RANGES["voice"]        # the same SynthVoice members; the source is the bank below
 RANGES["chain"] = RANGES["chorus"] + RANGES["pitchshift"] + RANGES["dattorro"]
 # random per-instance pre-delay in [0, 1] x 4800 samples (section 8d's gather-path variant)
 RANGES["dattorro_rpd"] = [(0, 1)] + RANGES["dattorro"][1:]
@@ -69,6 +70,13 @@ def instance_params(kind: str, first: int, count: int, seed: int = 0) -> np.ndar
             lo, hi = r
             rows.append((lo + (hi - lo) * uniform01(seed, f, first, count)).astype(np.float32))
     return np.stack(rows)
+
+
+def sample_bank(lengths, seed: int = 0) -> List[np.ndarray]:
+    """A seeded bank for the sample voices: sample k is `lengths[k]` frames of uniform noise in
+    [-0.5, 0.5), float32, a hash of (seed, k, frame) -- the same bank wherever it is generated."""
+    return [(uniform01(seed ^ 0x5A, k & 0xFF, (k >> 8) << 32, int(m)) - 0.5).astype(np.float32)
+            for k, m in enumerate(lengths)]
 
 
 def voice_notes(first: int, count: int) -> np.ndarray:
