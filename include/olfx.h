@@ -26,6 +26,10 @@
  *   olfx_sample_bank / olfx_sample_voices <- ol::synth::Sample over its data source and its setters
  *                                  (modules/synthlib/Sample.h:16-51, Sample.cpp:9-62) behind
  *                                  SampleSoundSource<1> (SampleSoundSource.h:13-40)
+ *   OLFX_KIND_SYNTH             <- the Daisy synth firmware as a whole (modules/ol_daisy/app/synth/main.cpp):
+ *                                  its globals (:49-67: four SynthVoices behind a Polyvoice, delay_fx,
+ *                                  reverb_fx, filter_fx) are one instrument, its audio callback (:78-86) one
+ *                                  olfx_process, handleMidi (:187-214) olfx_note_events and olfx_control
  *   olfx_last_error             <- (reference has none: void returns / NULL, verb.cpp:89-90,227)
  *
  * Audio layout (both host and device pointers accepted, see OLFX_IO_*):
@@ -77,12 +81,21 @@ enum {
                                   ol::fx::Reverb interface (Reverb.h:44-65) is the DattorroVerb_set* list and
                                   ReverbFx.cpp:11-37 still holds the glue, commented out.  OLFX_PR_* fields. */
     /* 9 stays unassigned: tests/test_platerack_host.py pins it as "a kind nobody has" (OLFX_E_KIND) */
-    OLFX_KIND_VOICE_SAMPLE = 10 /* SynthVoice(SampleSoundSource<1>(Sample), SvfFilter): sample playback from a
+    OLFX_KIND_VOICE_SAMPLE = 10, /* SynthVoice(SampleSoundSource<1>(Sample), SvfFilter): sample playback from a
                                   device-resident bank (olfx_sample_bank / olfx_sample_voices) -> SVF LP -> amp
                                   env; mono out, no input.  OLFX_VC_* parameters, note events, control changes,
                                   olfx_set_member, olfx_update and the voice buses as OLFX_KIND_VOICE.  GateOn /
                                   NoteOn also Seek(0) and Play() the sample, GateOff / NoteOff Pause() it
                                   (SampleSoundSource.h:21-26); SetFreq only stores the pitch (:28-30). */
+    OLFX_KIND_SYNTH = 11       /* the Daisy synth firmware's audio callback (ol_daisy/app/synth/main.cpp:78-86) in
+                                  one launch (synth.hip): per instrument, P MoogFilter SynthVoices behind a
+                                  Polyvoice (mono = 0; mono += v[0]; ... += v[P-1]) -> DelayFx<1> -> stereo copy
+                                  -> ReverbFx<2> over the ReverbSc stub -> FilterFx<2> in place.  No input;
+                                  out [2][n_frames][n_inst]: channel 0 is filter_fx's output, channel 1 the
+                                  reverb's channel 1, which FilterFx<2> leaves in place -- bit for bit what
+                                  OLFX_KIND_VOICE_MOOG + olfx_mix + OLFX_KIND_FXRACK at OLFX_FR_TOPOLOGY 1 give
+                                  for the sum in input channel 0.  P = 4 (olfx_create) or 1..8
+                                  (olfx_create_synth).  OLFX_SY_* fields and rules below. */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -185,6 +198,42 @@ enum {
 #define OLFX_PR_VERB0     (OLFX_FR_NPARAMS)
 #define OLFX_PR_NPARAMS   (OLFX_FR_NPARAMS + OLFX_DT_NPARAMS)
 
+/* Synth (OLFX_KIND_SYNTH): the sixteen voice fields (OLFX_VC_*), then the rack's twelve (OLFX_FR_*).
+     field                      meaning                                            default, validation
+     OLFX_SY_VOICE0 + OLFX_VC_* the Voice::Config member of ALL voices of the      as OLFX_KIND_VOICE_MOOG
+                                instrument (Polyvoice fans UpdateConfig, Update
+                                and both control calls out to every voice,
+                                Polyvoice.h:53-67)
+     OLFX_SY_RACK0 + OLFX_FR_*  delay_fx / reverb_fx / filter_fx members           as OLFX_KIND_FXRACK, but
+                                                                                   TOPOLOGY defaults to 1 and only
+                                                                                   1 is accepted (else OLFX_E_ARG,
+                                                                                   nothing changes); MASTER_VOLUME
+                                                                                   is stored and ignored
+   olfx_set_params / olfx_set_param / olfx_set_param_list / olfx_get_param work on the 28 fields; a write
+   that touches a voice field is UpdateConfig + Update of every voice of the instrument.  olfx_set_member on
+   a voice field is the voice kind's member-without-Update for all P voices (the firmware's set-up, main.cpp:
+   114-128 before Init at :149-154); on a rack field it is olfx_set_param.  olfx_update is Polyvoice::Update.
+   Note events (olfx_note_events / olfx_voice_events; `inst` is the instrument) are Polyvoice's calls
+   (Polyvoice.h:35-77), routed on the host at the call and queued per voice for the next block boundary:
+     NOTE_ON        the first voice with Playing() == 0 gets NoteOn; none free: the event is dropped
+     NOTE_OFF       the first voice with Playing() == note gets NoteOff
+     GATE_ON / OFF  every voice
+     SET_FREQUENCY  accepted, does nothing (Polyvoice.h:77)
+   Playing() is the last NoteOn's note and 0 after NoteOff (SynthVoice.h:245-260) and changes at the call;
+   olfx_synth_playing reads it back; olfx_reset clears it.  The reference's quirks are kept: NoteOn(0) gates
+   a voice whose Playing() stays 0, so the voice stays "free" and the next NoteOn takes it again; NoteOff(0)
+   hits the first free voice (Playing() == 0 == note) and gates it off.
+   Controls: olfx_control on an instrument is the firmware's handleMidi (main.cpp:201-207): the event goes
+   in turn to the voices (SynthVoice's mapping, every voice), delay_fx, reverb_fx and filter_fx (the rack's
+   topology-1 mapping), so CCs 41-44 move both the voice filter and FILTER_*; hardware-source events follow
+   the same route through the UpdateHardwareControl handlers.  olfx_synth_control_map gives the fields hit;
+   olfx_control_map(OLFX_KIND_SYNTH, ...) returns OLFX_E_KIND (it has one field to give).
+   Refused on this kind, with the code each call uses for a wrong kind (OLFX_E_STATE): olfx_mix_config and
+   olfx_mix (there are no buses: the sum never leaves the kernel), olfx_sample_bank, olfx_sample_voices. */
+#define OLFX_SY_VOICE0    0
+#define OLFX_SY_RACK0     (OLFX_VC_NPARAMS)
+#define OLFX_SY_NPARAMS   (OLFX_VC_NPARAMS + OLFX_FR_NPARAMS)
+
 /* ---- note events (voices) ----
    The ol::synth::Voice calls that change a voice's gate or pitch (Voice.h:33-57), as SynthVoice
    implements them (SynthVoice.h:231-268):
@@ -261,6 +310,10 @@ int olfx_kind_info_get(int kind, float sample_rate, olfx_kind_info *info);
    block = the frames per olfx_process call the caller intends (any multiple of 4 is accepted). */
 int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32_t block,
                 olfx_engine **out);
+/* An OLFX_KIND_SYNTH engine of n_inst instruments with `voices` (1..8) SynthVoices each;
+   olfx_create(OLFX_KIND_SYNTH, ...) is the firmware's 4. */
+int olfx_create_synth(int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                      olfx_engine **out);
 int olfx_destroy(olfx_engine *e);
 
 /* Zero all state and restore defaults (== destroy + create, without reallocating).  Like
@@ -297,8 +350,13 @@ int olfx_get_param(olfx_engine *e, uint32_t inst, uint32_t field, float *value);
 
 /* Map one control change to (field, value) exactly as the reference handler scales it
    (ol::core::scale, corelib/ol_corelib.h:31-44).  Returns OLFX_OK, OLFX_IGNORED, or an error.
-   Pure host function: no engine, no device. */
+   Pure host function: no engine, no device.  OLFX_KIND_SYNTH: OLFX_E_KIND -- a control can hit two of its
+   fields, see olfx_synth_control_map. */
 int olfx_control_map(int kind, uint8_t control, int source, float value, uint32_t *field, float *param_value);
+/* The same for an OLFX_KIND_SYNTH instrument (the firmware's handleMidi fan-out, main.cpp:201-207): the
+   voices' mapping first (OLFX_SY_VOICE0 + ..., or OLFX_FIELD_UPDATE_ONLY), then the rack's topology-1
+   mapping (OLFX_SY_RACK0 + ...).  Returns the number of fields hit (0..2) or an error.  Pure host function. */
+int olfx_synth_control_map(uint8_t control, int source, float value, uint32_t field[2], float param_value[2]);
 /* Apply control changes in order (each: the mapped olfx_set_param; ignored controls skipped).
    Replaces UpdateMidiControl / UpdateHardwareControl per instance. */
 int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
@@ -307,6 +365,8 @@ int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
 int olfx_note_events(olfx_engine *e, const olfx_event *ev, uint32_t n);
 /* The same queue with SET_FREQUENCY (Voice::SetFrequency, SynthVoice.h:264-267) as well. */
 int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n);
+/* OLFX_KIND_SYNTH: Playing() of the `voices` voices of instrument inst, as of the calls made so far. */
+int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);
 
 /* Update() of instances [first, first + count) with their current parameters (SynthVoice.h:66-98,
    Fx.h Update()): for voices, the first Update() ends SynthVoice::Init's component defaults
@@ -378,6 +438,7 @@ uint32_t olfx_num_instances(const olfx_engine *e);
 int      olfx_kind(const olfx_engine *e);
 uint64_t olfx_frames_processed(const olfx_engine *e);   /* per instance, since create/reset */
 uint32_t olfx_num_buses(const olfx_engine *e);          /* voice buses (olfx_mix_config) */
+uint32_t olfx_synth_voices(const olfx_engine *e);       /* voices per instrument (OLFX_KIND_SYNTH), else 0 */
 /* Algorithmic ("compulsory") HBM bytes per instance-frame of the dominant kernel, the figure
    bench.py's roofline uses. */
 double   olfx_algorithmic_bytes_per_frame(const olfx_engine *e);

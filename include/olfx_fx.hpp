@@ -116,6 +116,7 @@ public:
     void reset() { check(olfx_reset(e_), e_, "olfx_reset"); }
 
 protected:
+    explicit Engine(olfx_engine *created) : e_(created) {}   /* owns an engine a kind's own create call made */
     void ctl(uint32_t i, uint8_t control, int source, float value) {
         olfx_control_event ev{};
         ev.inst = i; ev.control = control; ev.source = (uint8_t)source; ev.value = value;
@@ -215,6 +216,56 @@ public:
     void SetDecayDiffusion(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION, v); }
     void SetDecay(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DECAY, v); }
     void SetDamping(uint32_t i, float v) { set(i, OLFX_PR_VERB0 + OLFX_DT_DAMPING, v); }
+};
+
+/* The Daisy synth firmware over N instruments (OLFX_KIND_SYNTH; ol_daisy/app/synth/main.cpp): an
+   instrument is the firmware's globals (:49-67) -- `voices` MoogFilter SynthVoices behind a Polyvoice,
+   delay_fx, reverb_fx, filter_fx -- and Process its audio callback (:78-86) in one launch: no input,
+   [2][F][N] out (channel 0 filter_fx's output, channel 1 the reverb's).  NoteOn / NoteOff / GateOn /
+   GateOff are Polyvoice's (allocation on the host at the call, Polyvoice.h:35-75); UpdateMidiControl /
+   UpdateHardwareControl are handleMidi's fan-out to the voices and the three effects (:201-207). */
+class SynthBank : public Engine {
+public:
+    SynthBank(uint32_t n_inst, float sample_rate, uint32_t voices = 4, uint32_t block = 256, int device = 0)
+        : Engine(make(n_inst, sample_rate, voices, block, device)) {}
+    uint32_t voices() const { return olfx_synth_voices(e_); }
+    /* Polyvoice::UpdateConfig + Update: every voice of the instrument */
+    void UpdateConfig(uint32_t i, const float config[OLFX_VC_NPARAMS]) {
+        set_block(i, 1, OLFX_SY_VOICE0, OLFX_VC_NPARAMS, config);
+    }
+    /* a SynthVoice member of every voice without Update() (the firmware's set-up before Init) */
+    void SetMember(uint32_t i, uint32_t voice_field, float v) {
+        check(olfx_set_member(e_, i, OLFX_SY_VOICE0 + voice_field, v), e_, "olfx_set_member");
+    }
+    void Update(uint32_t i) { check(olfx_update(e_, i, 1), e_, "olfx_update"); }
+    /* delay_fx / reverb_fx / filter_fx members (OLFX_FR_*) */
+    void SetRack(uint32_t i, uint32_t rack_field, float v) { set(i, OLFX_SY_RACK0 + rack_field, v); }
+    void NoteOn(uint32_t i, uint8_t midi_note, uint8_t velocity) { push(i, OLFX_EV_NOTE_ON, midi_note, velocity); }
+    void NoteOff(uint32_t i, uint8_t midi_note, uint8_t velocity) { push(i, OLFX_EV_NOTE_OFF, midi_note, velocity); }
+    void GateOn(uint32_t i) { push(i, OLFX_EV_GATE_ON, 0, 0); }
+    void GateOff(uint32_t i) { push(i, OLFX_EV_GATE_OFF, 0, 0); }
+    /* Playing() of each voice of instrument i, as of the calls made so far */
+    std::vector<uint8_t> Playing(uint32_t i) const {
+        std::vector<uint8_t> p(voices());
+        check(olfx_synth_playing(e_, i, p.data()), e_, "olfx_synth_playing");
+        return p;
+    }
+    /* frame_out [2][F][N] */
+    void Process(float *frame_out, uint32_t n_frames, int io = OLFX_IO_HOST, void *stream = nullptr) {
+        process(nullptr, frame_out, n_frames, io, stream);
+    }
+
+private:
+    static olfx_engine *make(uint32_t n_inst, float sample_rate, uint32_t voices, uint32_t block, int device) {
+        olfx_engine *e = nullptr;
+        check(olfx_create_synth(device, n_inst, voices, sample_rate, block, &e), nullptr, "olfx_create_synth");
+        return e;
+    }
+    void push(uint32_t i, uint8_t type, uint8_t note, uint8_t vel) {
+        olfx_event ev{};
+        ev.inst = i; ev.type = type; ev.note = note; ev.velocity = vel;
+        check(olfx_note_events(e_, &ev, 1), e_, "olfx_note_events");
+    }
 };
 
 /* ol::synth::SynthVoice over N voices (SynthVoice.h). The config array is in Voice::Config field

@@ -32,6 +32,7 @@ KIND_FXRACK = 6
 KIND_VOICE_MOOG = 7
 KIND_PLATERACK = 8
 KIND_VOICE_SAMPLE = 10      # 9 is unassigned (olfx.h)
+KIND_SYNTH = 11
 
 NO_SAMPLE = 0xFFFFFFFF
 SAMPLE_ONESHOT = 0
@@ -118,6 +119,7 @@ SIGNATURES = {
     "olfx_abi_version": (ctypes.c_int, []),
     "olfx_kind_info_get": (ctypes.c_int, [ctypes.c_int, _F, ctypes.POINTER(KindInfo)]),
     "olfx_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _U32, _F, _U32, ctypes.POINTER(_P)]),
+    "olfx_create_synth": (ctypes.c_int, [ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_destroy": (ctypes.c_int, [_P]),
     "olfx_reset": (ctypes.c_int, [_P]),
     "olfx_set_params": (ctypes.c_int, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(_F)]),
@@ -130,6 +132,8 @@ SIGNATURES = {
     "olfx_update": (ctypes.c_int, [_P, _U32, _U32]),
     "olfx_control_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_F)]),
+    "olfx_synth_control_map": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
+                                              ctypes.POINTER(_F)]),
     "olfx_control": (ctypes.c_int, [_P, ctypes.POINTER(ControlEvent), _U32]),
     "olfx_process": (ctypes.c_int, [_P, _P, _P, _U32, ctypes.c_int, _P]),
     "olfx_sync": (ctypes.c_int, [_P]),
@@ -144,6 +148,8 @@ SIGNATURES = {
     "olfx_mix_config": (ctypes.c_int, [_P, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "olfx_mix": (ctypes.c_int, [_P, _P, _P, _U32, ctypes.c_int, _P]),
     "olfx_num_buses": (_U32, [_P]),
+    "olfx_synth_voices": (_U32, [_P]),
+    "olfx_synth_playing": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint8)]),
     "olfx_sample_bank": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_F)]),
     "olfx_sample_voices": (ctypes.c_int, [_P, ctypes.POINTER(SampleVoice), _U32]),
     # include/olfx_sample.h: per-instance, per-sample operators (one block of latency)

@@ -186,7 +186,7 @@ size_t carve(olfx_engine *e, char *base) {
     };
     const int kind = e->kind;
     const size_t n = e->n, nd = e->n_dt;
-    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK) {
+    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK || kind == OLFX_KIND_SYNTH) {
         take(e->fr_ring, (size_t)kFrMaxDelay * 2 * n * 4);
         take(e->fr_state, (size_t)FRS_N * n * 4);
         take(e->fr_coef, (size_t)FRC_N * n * 4);
@@ -213,6 +213,11 @@ size_t carve(olfx_engine *e, char *base) {
         take(e->vc_coef, (size_t)VCC_N * n * 4);
     }
     if (kind == OLFX_KIND_VOICE_SAMPLE) take(e->sm_asg, (size_t)SMC_N * n * 4);
+    if (kind == OLFX_KIND_SYNTH) {
+        // every voice slot's state (voices x n rounded up to 64); one set of coefficients per instrument
+        take(e->vc_state, (size_t)VCS_N_MOOG * e->hs.n_ev() * 4);
+        take(e->vc_coef, (size_t)VCC_N * n * 4);
+    }
     return off;
 }
 
@@ -241,6 +246,7 @@ uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: dst[0] = e->vc_coef; break;
     case OLFX_KIND_VOICE_SAMPLE: dst[0] = e->vc_coef; dst[1] = e->sm_asg; break;
+    case OLFX_KIND_SYNTH: dst[0] = e->vc_coef; dst[1] = e->fr_coef; break;
     default: break;
     }
     a->nseg = sg.nseg;
@@ -315,7 +321,7 @@ int grow_slot(olfx_engine *e, olfx_engine::Slot &sl, size_t words, bool device_h
 int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Slot **used_slot) {
     *used_slot = nullptr;
     host::Shadow &hs = e->hs;
-    const bool evs = is_voice_kind(e->kind) && !hs.events.empty();
+    const bool evs = host::takes_note_events(e->kind) && !hs.events.empty();
     const size_t m = hs.dirty_list.size();
     if (!m && !evs) return OLFX_OK;
     using clk = std::chrono::steady_clock;
@@ -379,7 +385,7 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     }
     if (evs) {
         va->ev = reinterpret_cast<const uint2 *>(dev + pl.o_ev);
-        va->ev_more = va->ev + (size_t)((e->n + 63u) / 64u) * kVevCap;
+        va->ev_more = va->ev + (size_t)((hs.n_ev() + 63u) / 64u) * kVevCap;
     }
     lap(5);
     return OLFX_OK;
@@ -571,6 +577,26 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_platerack(a, s);
         break;
     }
+    case OLFX_KIND_SYNTH: {
+        // one fused launch: the voice waves feed the delay waves and the filter wave through LDS
+        SynthArgs a{};
+        a.ring = e->fr_ring;
+        a.fr_state = e->fr_state;
+        a.fr_coef = e->fr_coef;
+        a.vc_state = e->vc_state;
+        a.vc_coef = e->vc_coef;
+        a.out = dout;
+        a.plane = plane;
+        a.n = e->n;
+        a.n_frames = n_frames;
+        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
+        a.voices = e->hs.voices;
+        a.npad = e->hs.npad;
+        a.ev = ev.ev;
+        a.ev_more = ev.ev_more;
+        r = launch_synth(a, s);
+        break;
+    }
     case OLFX_KIND_CHAIN: {
         // one fused launch: chorus and pitch-shift waves feed the reverb wave through LDS
         ChainArgs a{};
@@ -674,15 +700,36 @@ int olfx_kind_info_get(int kind, float sample_rate, olfx_kind_info *info) {
     return OLFX_OK;
 }
 
+static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                         olfx_engine **out);
+
 int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32_t block,
                 olfx_engine **out) {
+    return create_engine(kind, device, n_inst, host::kSynthDefaultVoices, sample_rate, block, out);
+}
+
+int olfx_create_synth(int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                      olfx_engine **out) {
+    if (!out) return OLFX_E_ARG;
+    *out = nullptr;
+    if (voices < 1 || voices > host::kSynthMaxVoices) {
+        set_global_error("olfx_create_synth: %u voices per instrument (1..%u)", voices, host::kSynthMaxVoices);
+        return OLFX_E_ARG;
+    }
+    return create_engine(OLFX_KIND_SYNTH, device, n_inst, voices, sample_rate, block, out);
+}
+
+static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                         olfx_engine **out) {
     if (!out) return OLFX_E_ARG;
     *out = nullptr;
     if (!host::n_params_of(kind)) {
         set_global_error("olfx_create: unknown kind %d", kind);
         return OLFX_E_KIND;
     }
-    if (n_inst == 0 || !(sample_rate > 1000.f && sample_rate <= 384000.f) || block == 0 || (block & 3u)) {
+    // (the synth's voice slots, voices x n rounded up to 64, are indexed in 32 bits)
+    const bool too_many = kind == OLFX_KIND_SYNTH && ((uint64_t)n_inst + 63u) / 64u * 64u * voices > 0x7FFFFFFFull;
+    if (n_inst == 0 || too_many || !(sample_rate > 1000.f && sample_rate <= 384000.f) || block == 0 || (block & 3u)) {
         set_global_error("olfx_create: bad argument (n_inst=%u sr=%g block=%u)", n_inst, sample_rate, block);
         return OLFX_E_ARG;
     }
@@ -701,7 +748,7 @@ int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32
     e->device = device;
     e->n = n_inst;
     e->block = block;
-    e->hs.init(kind, n_inst, sample_rate);
+    e->hs.init(kind, n_inst, sample_rate, voices);
     e->trace = std::getenv("OLFX_TRACE_CONTROL") && std::getenv("OLFX_TRACE_CONTROL")[0] == '1';
     if (const char *cb = std::getenv("OLFX_COPY_BYTES"))
         e->copy_bytes = std::min<size_t>((size_t)std::strtoull(cb, nullptr, 10), olfx_engine::kCopyBytes);
@@ -736,7 +783,7 @@ int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32
     // slots allocated now, so that no block -- an all-voices note-off in the middle of a stream,
     // say -- pays a pinned / device allocation: the small ones at the copy threshold, the big ones
     // for the largest packet this engine can produce (up to 256 MiB each; larger on first need)
-    const size_t maxw = host::max_packet_words(kind, n_inst);
+    const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev());
     for (olfx_engine::Slot &sl : e->slot)
         if (!rc) rc = grow_slot(e, sl, olfx_engine::kCopyBytes / 4, false);
     if (maxw * 4 >= e->copy_bytes && maxw * 4 <= ((size_t)256 << 20))
@@ -826,6 +873,10 @@ int olfx_note_events(olfx_engine *e, const olfx_event *ev, uint32_t n) {
 
 int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n) {
     return e ? e->report(e->hs.voice_events(ev, n)) : OLFX_E_ARG;
+}
+
+int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing) {
+    return e ? e->report(e->hs.synth_playing(inst, playing)) : OLFX_E_ARG;
 }
 
 int olfx_update(olfx_engine *e, uint32_t first, uint32_t count) {
@@ -1037,6 +1088,7 @@ uint32_t olfx_num_instances(const olfx_engine *e) { return e ? e->n : 0; }
 int olfx_kind(const olfx_engine *e) { return e ? e->kind : 0; }
 uint64_t olfx_frames_processed(const olfx_engine *e) { return e ? e->frames : 0; }
 uint32_t olfx_num_buses(const olfx_engine *e) { return e ? e->n_buses : 0; }
+uint32_t olfx_synth_voices(const olfx_engine *e) { return e ? e->hs.voices : 0; }
 
 double olfx_algorithmic_bytes_per_frame(const olfx_engine *e) {
     return e ? host::algorithmic_bytes_per_frame(e->kind) : 0.0;
@@ -1058,6 +1110,7 @@ const char *olfx_kernel_name(const olfx_engine *e) {
     case OLFX_KIND_CHAIN: return "chain_block_v5";
     case OLFX_KIND_FXRACK: return "fxrack_block_v3";
     case OLFX_KIND_PLATERACK: return "platerack_block_v1";
+    case OLFX_KIND_SYNTH: return "synth_block_v1";
     default: return "";
     }
 }

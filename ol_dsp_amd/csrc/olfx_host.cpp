@@ -23,7 +23,8 @@ uint32_t pow2_at_least(uint32_t x) {
 float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // the most parameters a kind has (an instance's parameters on the stack)
-constexpr uint32_t kMaxParams = std::max({(uint32_t)OLFX_CN_NPARAMS, (uint32_t)OLFX_VC_NPARAMS, (uint32_t)OLFX_PR_NPARAMS});
+constexpr uint32_t kMaxParams = std::max({(uint32_t)OLFX_CN_NPARAMS, (uint32_t)OLFX_VC_NPARAMS, (uint32_t)OLFX_PR_NPARAMS,
+                                          (uint32_t)OLFX_SY_NPARAMS});
 
 // a fraction of a cycle in [0, 1] as 64-bit fixed point (2^64 = one cycle); 1.0 wraps to 0
 uint64_t fix64(double cycles) {
@@ -56,11 +57,12 @@ uint32_t n_params_of(int kind) {
     case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
     case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
     case OLFX_KIND_PLATERACK: return OLFX_PR_NPARAMS;
+    case OLFX_KIND_SYNTH: return OLFX_SY_NPARAMS;
     default: return 0;
     }
 }
 
-uint32_t in_channels(int kind) { return is_voice_kind(kind) ? 0u : 2u; }
+uint32_t in_channels(int kind) { return is_voice_kind(kind) || kind == OLFX_KIND_SYNTH ? 0u : 2u; }
 uint32_t out_channels(int kind) { return is_voice_kind(kind) ? 1u : 2u; }
 
 // ol::core::scale (modules/corelib/ol_corelib.h:27-44), t_sample = float
@@ -154,6 +156,13 @@ void default_params(int kind, float *p) {
         p[OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION] = 0.5f;    // decay_diffusion
         p[OLFX_PR_VERB0 + OLFX_DT_DECAY] = 0.5f;              // decay_time
         break;
+    case OLFX_KIND_SYNTH:
+        // the firmware's objects (main.cpp:49-67): SynthVoice members, then delay_fx / reverb_fx /
+        // filter_fx as the rack's members, in the callback's topology
+        default_params(OLFX_KIND_VOICE_MOOG, p + OLFX_SY_VOICE0);
+        default_params(OLFX_KIND_FXRACK, p + OLFX_SY_RACK0);
+        p[OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY] = 1.f;
+        break;
     default: break;
     }
 }
@@ -182,6 +191,9 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
     case OLFX_KIND_FXRACK: return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n;
     case OLFX_KIND_PLATERACK:       // the rack's ring + the plate's, the plate's instances padded to 64
         return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n + dt * ((n + 63u) & ~63u);
+    case OLFX_KIND_SYNTH:           // the rack's, one set of voice coefficients, four voices' state
+        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4 + VCC_N * 4 +
+                (uint64_t)kSynthDefaultVoices * VCS_N_MOOG * 4) * n;
     default: return 0;
     }
 }
@@ -198,6 +210,7 @@ double algorithmic_bytes_per_frame(int kind) {
     case OLFX_KIND_CHAIN: return 228.6;
     case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
     case OLFX_KIND_PLATERACK: return 32.0 + 164.6 - 16.0;   // rack + plate - the plate's own I/O (in LDS now)
+    case OLFX_KIND_SYNTH: return 32.0 - 8.0;   // the rack at topology 1 with no input read: ring 8 + 8, out 8
     default: return 0.0;
     }
 }
@@ -215,6 +228,7 @@ double algorithmic_read_bytes_per_frame(int kind) {
     case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
     case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
     case OLFX_KIND_PLATERACK: return 16.0 + 6445.0 * 4.0 / 256.0;   // rack + the plate's taps (its input is in LDS)
+    case OLFX_KIND_SYNTH: return 16.0 - 8.0;   // the ring read; the input never leaves LDS
     default: return 0.0;
     }
 }
@@ -421,6 +435,7 @@ Segments coef_segments(int kind) {
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
     case OLFX_KIND_VOICE_SAMPLE: return {2, {VCC_N, SMC_N, 0}};   // the voice, its Sample
+    case OLFX_KIND_SYNTH: return {2, {VCC_N, FRC_N, 0}};          // the instrument's voices, its rack
     default: return {0, {0, 0, 0}};
     }
 }
@@ -456,6 +471,11 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
         std::memcpy(w, fc, VCC_N * 4);
         if (kind == OLFX_KIND_VOICE_SAMPLE) sample_record(i, w + VCC_N);
         break;
+    case OLFX_KIND_SYNTH:
+        derive_voice(p + OLFX_SY_VOICE0, configured[i] != 0, true, sr, fc);
+        std::memcpy(w, fc, VCC_N * 4);
+        derive_fxrack(p + OLFX_SY_RACK0, sr, w + VCC_N);
+        break;
     default: break;
     }
 }
@@ -481,7 +501,8 @@ void Shadow::reset() {
     n_components = 0;
     pre_changed = true;
     events.clear();
-    ev_slot.assign(n, -1);
+    ev_slot.assign(n_ev(), -1);
+    playing.assign((size_t)voices * n, 0);
     dirty_list.clear();
     dirty_mark.assign(n, 0);
     mark_dirty(0, n);                        // every coefficient is derived at the first block
@@ -509,6 +530,9 @@ const char *Shadow::bad_value(uint32_t field, float v) const {
     // the components alone (2..4) are the firmware's objects around the ReverbSc stub: no plate in them
     if (kind == OLFX_KIND_PLATERACK && field == OLFX_PR_RACK0 + OLFX_FR_TOPOLOGY && !(v == 0.f || v == 1.f))
         return "plate rack topology must be 0 or 1";
+    // the firmware's callback is the only chain the synth kernel runs
+    if (kind == OLFX_KIND_SYNTH && field == OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY && v != 1.f)
+        return "synth rack topology must be 1";
     return nullptr;
 }
 
@@ -532,7 +556,7 @@ int Shadow::set_range(uint32_t first, uint32_t count, uint32_t field0, uint32_t 
                 return fail(OLFX_E_ARG, "olfx_set_params: %s", why);
     for (uint32_t f = 0; f < n_fields; ++f)
         for (uint32_t k = 0; k < count; ++k) store_param(field0 + f, first + k, values[(size_t)f * count + k]);
-    if (is_voice_kind(kind))
+    if (touches_voice(field0, n_fields))
         for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
     mark_dirty(first, count);
     return OLFX_OK;
@@ -547,14 +571,15 @@ int Shadow::set_list(uint32_t field, const uint32_t *inst, const float *values, 
     }
     for (uint32_t k = 0; k < count; ++k) {
         store_param(field, inst[k], values[k]);
-        if (is_voice_kind(kind)) configured[inst[k]] = 1;
+        if (touches_voice(field, 1)) configured[inst[k]] = 1;
         mark_dirty(inst[k], 1);
     }
     return OLFX_OK;
 }
 
 int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
-    if (!is_voice_kind(kind)) return set_range(inst, 1, field, 1, &value);
+    // (the synth: a voice field is the member of all its voices, a rack field is olfx_set_param)
+    if (!touches_voice(field, 1)) return set_range(inst, 1, field, 1, &value);
     if (inst >= n || field >= n_params) return fail(OLFX_E_ARG, "olfx_set_member: out of range");
     if (const char *why = bad_value(field, value)) return fail(OLFX_E_ARG, "olfx_set_member: %s", why);
     // SynthVoice::Process reads filter_cutoff, filter_env_amount and amp_env_amount itself every
@@ -575,7 +600,7 @@ int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
 
 int Shadow::update(uint32_t first, uint32_t count) {
     if ((uint64_t)first + count > n) return fail(OLFX_E_ARG, "olfx_update: range out of bounds");
-    if (is_voice_kind(kind))
+    if (takes_note_events(kind))
         for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
     mark_dirty(first, count);
     return OLFX_OK;
@@ -683,6 +708,22 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
+        if (kind == OLFX_KIND_SYNTH) {
+            // handleMidi (main.cpp:201-207): the voices, then delay_fx, reverb_fx, filter_fx
+            uint32_t fields[2];
+            float vals[2];
+            const int hits = olfx_synth_control_map(ev[k].control, ev[k].source, ev[k].value, fields, vals);
+            if (hits < 0) return fail(hits, "olfx_control: event %u", k);
+            for (int h = 0; h < hits; ++h) {
+                if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {    // the voices' Update() with unchanged members
+                    configured[ev[k].inst] = 1;
+                    mark_dirty(ev[k].inst, 1);
+                } else if (const int r2 = set_range(ev[k].inst, 1, fields[h], 1, &vals[h])) {
+                    return r2;
+                }
+            }
+            continue;
+        }
         uint32_t field;
         float v;
         uint8_t control = ev[k].control;
@@ -719,26 +760,74 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
 }
 
 int Shadow::note_events(const olfx_event *ev, uint32_t count) {
-    if (!is_voice_kind(kind)) return fail(OLFX_E_STATE, "olfx_note_events: not a voice engine");
+    if (!takes_note_events(kind)) return fail(OLFX_E_STATE, "olfx_note_events: not a voice engine");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_note_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_GATE_OFF)
             return fail(OLFX_E_ARG, "olfx_note_events: bad event %u", k);
     }
-    for (uint32_t k = 0; k < count; ++k)
-        events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
+    for (uint32_t k = 0; k < count; ++k) {
+        if (kind == OLFX_KIND_SYNTH) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        else events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
+    }
     return OLFX_OK;
 }
 
 int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
-    if (!is_voice_kind(kind)) return fail(OLFX_E_STATE, "olfx_voice_events: not a voice engine");
+    if (!takes_note_events(kind)) return fail(OLFX_E_STATE, "olfx_voice_events: not a voice engine");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_voice_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_SET_FREQUENCY ||
             (ev[k].type == OLFX_EV_SET_FREQUENCY && !std::isfinite(ev[k].value)))
             return fail(OLFX_E_ARG, "olfx_voice_events: bad event %u", k);
     }
+    if (kind == OLFX_KIND_SYNTH) {
+        for (uint32_t k = 0; k < count; ++k) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        return OLFX_OK;
+    }
     events.insert(events.end(), ev, ev + count);
+    return OLFX_OK;
+}
+
+// ol::synth::Polyvoice's calls on instrument `inst` (Polyvoice.h:35-77) as events of its voices (voice
+// slot p * npad + inst).  Playing() changes here, at the call, as SynthVoice's does (SynthVoice.h:
+// 245-260: NoteOn stores the note, NoteOff stores 0).  The reference's quirks follow from the same
+// tests: NoteOn(0) leaves Playing() at 0, so the voice is gated yet still "free"; NoteOff(0) matches
+// the first voice with Playing() == 0.
+void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
+    auto push = [&](uint32_t p) {
+        events.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
+    };
+    uint8_t *pl = playing.data() + inst;                 // voice p: pl[p * n]
+    switch (type) {
+    case OLFX_EV_NOTE_ON:
+        for (uint32_t p = 0; p < voices; ++p)
+            if (!pl[(size_t)p * n]) {
+                push(p);
+                pl[(size_t)p * n] = note;
+                break;
+            }
+        break;                                            // none free: dropped
+    case OLFX_EV_NOTE_OFF:
+        for (uint32_t p = 0; p < voices; ++p)
+            if (pl[(size_t)p * n] == note) {
+                push(p);
+                pl[(size_t)p * n] = 0;
+                break;
+            }
+        break;
+    case OLFX_EV_GATE_ON:
+    case OLFX_EV_GATE_OFF:
+        for (uint32_t p = 0; p < voices; ++p) push(p);
+        break;
+    default: break;                                       // SetFrequency: a nop (Polyvoice.h:77)
+    }
+}
+
+int Shadow::synth_playing(uint32_t inst, uint8_t *out) {
+    if (kind != OLFX_KIND_SYNTH) return fail(OLFX_E_STATE, "olfx_synth_playing: not a synth engine");
+    if (inst >= n || !out) return fail(OLFX_E_ARG, "olfx_synth_playing: bad argument");
+    for (uint32_t p = 0; p < voices; ++p) out[p] = playing[(size_t)p * n + inst];
     return OLFX_OK;
 }
 
@@ -796,7 +885,7 @@ void Shadow::fold_events() {
     events.clear();
     // records per workgroup (64 voices); crowded workgroups (more than kVevCap records) get a run
     // of the overflow list each, in group order
-    const uint32_t groups = (n + 63u) / 64u;
+    const uint32_t groups = (n_ev() + 63u) / 64u;
     ev_count.assign(groups, 0u);
     for (const Folded &r : folded) {
         ev_count[r.inst >> 6]++;
@@ -814,7 +903,7 @@ void Shadow::fold_events() {
 // The folded records into a packet's event section (VoiceArgs::ev layout, olfx_internal.h):
 // `fix` = [groups][kVevCap] 8-B slots, then the overflow list.
 void Shadow::write_events(uint32_t *fix) {
-    const uint32_t groups = (n + 63u) / 64u;
+    const uint32_t groups = (n_ev() + 63u) / 64u;
     std::memset(fix, 0, (size_t)groups * kVevCap * 8);
     uint32_t *more = fix + (size_t)groups * kVevCap * 2;
     ev_fill.assign(groups, 0u);
@@ -832,19 +921,19 @@ void Shadow::write_events(uint32_t *fix) {
         }
 }
 
-PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more) {
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev) {
     PacketPlan pl;
     pl.dense = m == n;                                   // every instance: no instance list
     pl.o_inst = 0;
     pl.o_val = pl.o_inst + (pl.dense ? 0 : up4(m));
     pl.o_ev = up4(pl.o_val + (size_t)W * m);
-    pl.words = pl.o_ev + (evs ? 2 * ((size_t)((n + 63u) / 64u) * kVevCap + n_more) : 0);
+    pl.words = pl.o_ev + (evs ? 2 * ((size_t)(((n_ev ? n_ev : n) + 63u) / 64u) * kVevCap + n_more) : 0);
     return pl;
 }
 
-size_t max_packet_words(int kind, uint32_t n_inst) {
-    const size_t n = n_inst, W = coef_segments(kind).total();
-    const size_t ev = is_voice_kind(kind) ? 2 * ((n + 63) / 64 * kVevCap + n) : 0;
+size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev) {
+    const size_t n = n_inst, W = coef_segments(kind).total(), nv = n_ev ? n_ev : n_inst;
+    const size_t ev = takes_note_events(kind) ? 2 * ((nv + 63) / 64 * kVevCap + nv) : 0;
     return n + W * n + ev + 16;
 }
 
@@ -934,5 +1023,35 @@ extern "C" int olfx_control_map(int kind, uint8_t control, int source, float val
         default: return OLFX_IGNORED;              // incl. the reverb CCs that reach only the ReverbSc stub
         }
     }
-    return n_params_of(kind) ? OLFX_IGNORED : OLFX_E_KIND;
+    // the synth's controls can hit two fields: olfx_synth_control_map
+    return n_params_of(kind) && kind != OLFX_KIND_SYNTH ? OLFX_IGNORED : OLFX_E_KIND;
+}
+
+// handleMidi's fan-out (main.cpp:201-207), from the two kinds' tables above: the voices' handler, then
+// the rack's at topology 1 as Shadow::control routes it (DelayFx 35-39, ReverbFx's balance 34 -- its
+// other controls reach only the ReverbSc stub --, FilterFx 41-44 through the rack's 45-48 entries)
+extern "C" int olfx_synth_control_map(uint8_t control, int source, float value, uint32_t field[2], float param_value[2]) {
+    using namespace olfx::host;
+    if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
+    int hits = 0;
+    uint32_t f;
+    float v;
+    int rc = olfx_control_map(OLFX_KIND_VOICE_MOOG, control, source, value, &f, &v);
+    if (rc < 0) return rc;
+    if (rc == OLFX_OK) {
+        field[hits] = f == OLFX_FIELD_UPDATE_ONLY ? f : OLFX_SY_VOICE0 + f;
+        param_value[hits++] = v;
+    }
+    const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
+    const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
+    if (filter_cc || delay_cc || control == CC_REVERB_BALANCE) {
+        const uint8_t as = filter_cc ? (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF) : control;
+        rc = olfx_control_map(OLFX_KIND_FXRACK, as, source, value, &f, &v);
+        if (rc < 0) return rc;
+        if (rc == OLFX_OK) {
+            field[hits] = OLFX_SY_RACK0 + f;
+            param_value[hits++] = v;
+        }
+    }
+    return hits;
 }

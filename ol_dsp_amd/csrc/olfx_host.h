@@ -21,7 +21,10 @@ uint32_t in_channels(int kind);
 uint32_t out_channels(int kind);
 void default_params(int kind, float *p);     // the reference's defaults of the user-facing parameters
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize);
-uint64_t state_bytes(int kind, uint32_t n, float sr);
+uint64_t state_bytes(int kind, uint32_t n, float sr);      // OLFX_KIND_SYNTH: the 4-voice figure
+// kinds that take note events (the voices, and the synth through its Polyvoice router)
+inline bool takes_note_events(int kind) { return is_voice_kind(kind) || kind == OLFX_KIND_SYNTH; }
+constexpr uint32_t kSynthDefaultVoices = 4, kSynthMaxVoices = 8;
 double algorithmic_bytes_per_frame(int kind);
 double algorithmic_read_bytes_per_frame(int kind);
 
@@ -50,11 +53,11 @@ struct PacketPlan {
     size_t o_inst, o_val, o_ev, words;
 };
 // n instances of which m changed, W words per record, `evs`: an event section with n_more
-// overflow records
-PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more);
+// overflow records for n_ev voice slots (0: the n instances are the voices)
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0);
 // The largest packet an engine can produce: every instance's coefficients and, for voices, an
-// event for every voice (plan_packet's layout, rounded up).
-size_t max_packet_words(int kind, uint32_t n);
+// event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).
+size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0);
 
 struct Folded { uint32_t inst, op, freq, pad; };
 
@@ -96,12 +99,21 @@ struct Shadow {
     // reset() keeps both (and makes every Sample fresh)
     BankPlan bank;
     std::vector<SampleAsg> samples;       // [n]
+    // the synth: voices per instrument, n rounded up to 64, and every voice's Playing() ([voices][n]:
+    // the last NoteOn's note, 0 after NoteOff; SynthVoice.h:245-260).  Voice p of instrument i is voice
+    // slot p * npad + i of the event queue (SynthArgs, olfx_internal.h)
+    uint32_t voices = 0, npad = 0;
+    std::vector<uint8_t> playing;
     char msg[160] = "";
 
-    void init(int kind_, uint32_t n_, float sr_) {
+    void init(int kind_, uint32_t n_, float sr_, uint32_t voices_ = kSynthDefaultVoices) {
         kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_);
         samples.assign(kind_ == OLFX_KIND_VOICE_SAMPLE ? n_ : 0u, SampleAsg{});
+        voices = kind_ == OLFX_KIND_SYNTH ? voices_ : 0u;
+        npad = kind_ == OLFX_KIND_SYNTH ? (n_ + 63u) & ~63u : 0u;
     }
+    // the voice slots that note events address: the instances themselves, or the synth's voices
+    uint32_t n_ev() const { return kind == OLFX_KIND_SYNTH ? voices * npad : n; }
     // Every instance at the reference's defaults, unconfigured, all dirty; nothing queued.
     void reset();
 
@@ -112,6 +124,7 @@ struct Shadow {
     int control(const olfx_control_event *ev, uint32_t count);       // rack topology routing included
     int note_events(const olfx_event *ev, uint32_t count);
     int voice_events(const olfx_voice_event *ev, uint32_t count);
+    int synth_playing(uint32_t inst, uint8_t *out);                  // [voices]
     bool uniform_predelay() const;        // reverb: every instance has the same pre-delay in samples
     // olfx_sample_bank in two steps, so that the engine can allocate and copy in between: the layout of
     // a valid bank (nothing changes), then the switch to it (every Sample fresh; assignments whose index
@@ -126,7 +139,9 @@ struct Shadow {
     void derive_record(uint32_t i, uint32_t *w) const;
     // The queued events as one record per voice (`folded`) and their place in the event section.
     void fold_events();
-    PacketPlan plan(bool evs) const { return plan_packet(n, dirty_list.size(), coef_segments(kind).total(), evs, n_more); }
+    PacketPlan plan(bool evs) const {
+        return plan_packet(n, dirty_list.size(), coef_segments(kind).total(), evs, n_more, n_ev());
+    }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
     // The folded records into the event section `fix` (buf + o_ev).
@@ -137,6 +152,12 @@ private:
     const char *bad_value(uint32_t field, float v) const;
     void store_param(uint32_t field, uint32_t inst, float v);
     void mark_dirty(uint32_t first, uint32_t count);
+    // the synth's Polyvoice router (Polyvoice.h:35-77): one instrument event -> per-voice events
+    void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
+    // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
+    bool touches_voice(uint32_t field0, uint32_t n_fields) const {
+        return is_voice_kind(kind) || (kind == OLFX_KIND_SYNTH && n_fields && field0 < OLFX_SY_RACK0);
+    }
 };
 
 }  // namespace host

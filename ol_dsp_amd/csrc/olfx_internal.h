@@ -293,6 +293,27 @@ struct PlateRackArgs {
 };
 hipError_t launch_platerack(const PlateRackArgs &a, hipStream_t s);
 
+// The synth (synth.hip): `voices` MoogFilter SynthVoices per instrument, their Polyvoice sum, the
+// rack's topology 1, in one launch.  Voice p of instrument i is voice slot p * npad + i of the state
+// planes and the event slots (npad = n rounded up to 64: a 64-voice group is one voice slot of 64
+// consecutive instruments); the voice coefficients are the instrument's ([VCC_N][n]: Polyvoice fans
+// every setter out to all its voices).
+struct SynthArgs {
+    float *ring;                // [n][kFrMaxDelay][2]
+    uint32_t *fr_state;         // [FRS_N][n]
+    const uint32_t *fr_coef;    // [FRC_N][n]
+    float *vc_state;            // [VCS_N_MOOG][voices * npad]
+    const float *vc_coef;       // [VCC_N][n]
+    float *out;                 // [2][..][n]
+    uint64_t plane;
+    uint32_t n, n_frames;       // instruments; frames (multiple of 4)
+    uint32_t t0;                // rack ring position of the first frame: frames since create mod 48000
+    uint32_t voices, npad;
+    const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
+    const uint2 *ev_more;
+};
+hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
+
 hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_chorus(const ChorusArgs &a, hipStream_t s);

@@ -178,14 +178,16 @@ namespace fr {
 
 // The delay stage over the block's nf frames for the 32 instances from inst0 (< n; instances past n
 // mirror instance n - 1 and store nothing).  ring / state / coef: FxRackArgs'; t00: the ring position
-// of frame 0 (even); region: kRegion floats of LDS of this wave.  emit(c, av) takes chunk c's
-// DelayFx outputs of this lane's (instance, channel), av[k] for frame 16 c + k (frames past a short
-// last chunk are unspecified); in topology 1 (DelayFx<1>, then stereo[0] = stereo[1]) both lanes of
-// the instance give channel 0's.
-template <class Emit>
-__device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const uint32_t *coef, const float *in,
-                                            uint64_t plane, uint32_t n, uint32_t nf, uint32_t t00, float *region,
-                                            uint32_t lane, uint32_t inst0, Emit &&emit) {
+// of frame 0 (even); region: kRegion floats of LDS of this wave.  load(f0, Cx, xv) fills xv[k] with
+// this lane's (instance, channel) input of frame f0 + k for k < Cx and 0.f from Cx on (Cx = 0: a chunk
+// past the block's end); it is called for chunk c + 1 before chunk c is computed, chunk 0 first.
+// emit(c, av) takes chunk c's DelayFx outputs of this lane's (instance, channel), av[k] for frame
+// 16 c + k (frames past a short last chunk are unspecified); in topology 1 (DelayFx<1>, then
+// stereo[0] = stereo[1]) both lanes of the instance give channel 0's.
+template <class Load, class Emit>
+__device__ __forceinline__ void delay_stage_from(float *ring, uint32_t *state, const uint32_t *coef, uint32_t n,
+                                                 uint32_t nf, uint32_t t00, float *region, uint32_t lane,
+                                                 uint32_t inst0, Load &&load, Emit &&emit) {
     const uint32_t j = lane >> 1, chn = lane & 1u;
     const uint32_t i_raw = inst0 + j;
     const bool valid = i_raw < n;
@@ -205,8 +207,6 @@ __device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const 
 
     // the wave's 32 rings (12.3 MB) get their own descriptor, so 32-bit offsets cover any n
     const ch::Rsrc rR = ch::rsrc(ring + (size_t)inst0 * kFrMaxDelay * 2, (uint64_t)min(32u, n - inst0) * kFrMaxDelay * 8);
-    const ch::Rsrc rIn = ch::rsrc(in, (plane + (uint64_t)nf * n) * 4);
-    const uint32_t io_v = chn * (uint32_t)plane * 4u + i * 4u, frame_b = n * 4u;
 
     float *win = region;                                // [kSlots][64]
     float *wcol = win + lane;
@@ -215,8 +215,7 @@ __device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const 
 
     float x[kChunk], xn[kChunk], y[kChunk], y2[kChunk];
     int C = (int)min((uint32_t)kChunk, nf);
-#pragma unroll
-    for (int k = 0; k < kChunk; ++k) x[k] = k < C ? ch::ld1(rIn, io_v, (uint32_t)k * frame_b) : 0.f;
+    load(0u, C, x);
     load_line(lo, lcur);
     load_line(nx, next_line(lcur));
     for (uint32_t f0 = 0, c = 0; f0 < nf; f0 += kChunk, ++c) {
@@ -231,11 +230,7 @@ __device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const 
         // a chunk's ring run is stored at the start of the NEXT chunk, ahead of that chunk's loads
         if (f0 > 0) FR_FLUSH_RING(rR, n, inst0, lane, t00, stage, f0 - kChunk, kChunk)   // the previous chunk was full
         // ---- 2. the next chunk's inputs and new line in flight (unconditional); L + 1 is carried ----
-#pragma unroll
-        for (int k = 0; k < kChunk; ++k) {
-            const float vv = ch::ld1(rIn, io_v, min(f0 + kChunk + (uint32_t)k, nf - 1u) * frame_b);
-            xn[k] = k < Cn ? vv : 0.f;
-        }
+        load(f0 + kChunk, Cn, xn);
         FR_CARRY_LINES();
 #pragma unroll
         for (int k = 0; k < kChunk; ++k) y2[k] = y[k];
@@ -284,6 +279,28 @@ __device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const 
         state[FRS_DLOW * n + i] = __float_as_uint(slow);
         state[FRS_DBAND * n + i] = __float_as_uint(sband);
     }
+}
+
+// The stage with its input in HBM (the plate rack's D role): in is [2][..][n] with the channel planes
+// `plane` floats apart; every chunk's loads are issued unconditionally (clamped to the block's last
+// frame) a chunk ahead.
+template <class Emit>
+__device__ __forceinline__ void delay_stage(float *ring, uint32_t *state, const uint32_t *coef, const float *in,
+                                            uint64_t plane, uint32_t n, uint32_t nf, uint32_t t00, float *region,
+                                            uint32_t lane, uint32_t inst0, Emit &&emit) {
+    const uint32_t i = min(inst0 + (lane >> 1), n - 1);
+    const ch::Rsrc rIn = ch::rsrc(in, (plane + (uint64_t)nf * n) * 4);
+    const uint32_t io_v = (lane & 1u) * (uint32_t)plane * 4u + i * 4u, frame_b = n * 4u;
+    delay_stage_from(
+        ring, state, coef, n, nf, t00, region, lane, inst0,
+        [&](uint32_t f0, int Cx, float (&xv)[kChunk]) {
+#pragma unroll
+            for (int k = 0; k < kChunk; ++k) {
+                const float vv = ch::ld1(rIn, io_v, min(f0 + (uint32_t)k, nf - 1u) * frame_b);
+                xv[k] = k < Cx ? vv : 0.f;
+            }
+        },
+        emit);
 }
 
 }  // namespace fr

@@ -46,17 +46,20 @@ struct VoiceEv {
     uint32_t op;
     float freq;
 };
-__device__ __forceinline__ VoiceEv voice_event(const VoiceArgs &a, uint2 *slot, uint32_t lane, uint32_t me) {
+// `group`: the 64-voice group whose slots these are (a voice kernel's workgroup; the synth's voice
+// slot p of a 64-instrument group, synth.hip).
+__device__ __forceinline__ VoiceEv voice_event_of(const uint2 *evs, const uint2 *evs_more, uint2 *slot, uint32_t lane,
+                                                  uint32_t me, uint32_t group) {
     VoiceEv r{0u, 0.0f};
-    if (!a.ev) return r;
+    if (!evs) return r;
     uint2 e = make_uint2(0u, 0u);
-    if (lane < kVevCap) e = a.ev[blockIdx.x * kVevCap + lane];
+    if (lane < kVevCap) e = evs[group * kVevCap + lane];
     slot[lane] = make_uint2(0u, 0u);
     const uint32_t head = __builtin_amdgcn_readfirstlane(e.x);
     if ((head >> 8) & VEV_MORE) {
         const uint32_t cnt = head >> 16, first = __builtin_amdgcn_readfirstlane(e.y);
         e = make_uint2(0u, 0u);
-        if (lane < cnt) e = a.ev_more[first + lane];
+        if (lane < cnt) e = evs_more[first + lane];
     }
     if (e.x >> 8) slot[e.x & 63u] = make_uint2(e.x >> 8, e.y);
     // one wave writes and reads its slots: LDS operations of a wave complete in order; the fences
@@ -68,6 +71,10 @@ __device__ __forceinline__ VoiceEv voice_event(const VoiceArgs &a, uint2 *slot, 
     r.op = v.x;
     r.freq = __uint_as_float(v.y);
     return r;
+}
+// the voice kernels: the group is the workgroup
+__device__ __forceinline__ VoiceEv voice_event(const VoiceArgs &a, uint2 *slot, uint32_t lane, uint32_t me) {
+    return voice_event_of(a.ev, a.ev_more, slot, lane, me, blockIdx.x);
 }
 
 // Another wave's view of slots voice_event staged, after a workgroup barrier.

@@ -31,6 +31,7 @@ KIND_NAMES = {
     "voice_moog": _lib.KIND_VOICE_MOOG,
     "platerack": _lib.KIND_PLATERACK,
     "voice_sample": _lib.KIND_VOICE_SAMPLE,
+    "synth": _lib.KIND_SYNTH,
 }
 
 # parameter field names, in C-ABI order
@@ -54,6 +55,8 @@ PARAMS[_lib.KIND_CHAIN] = (["chorus_" + p for p in PARAMS[_lib.KIND_CHORUS]]
                            + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]])
 # the plate rack: the rack's fields, then the plate's (OLFX_PR_*)
 PARAMS[_lib.KIND_PLATERACK] = PARAMS[_lib.KIND_FXRACK] + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]]
+# the synth: the voices' fields, then the rack's (OLFX_SY_*; the two lists share filter_cutoff and others)
+PARAMS[_lib.KIND_SYNTH] = PARAMS[_lib.KIND_VOICE] + ["rack_" + p for p in PARAMS[_lib.KIND_FXRACK]]
 
 
 def kind_info(kind: int, sample_rate: float = 48000.0) -> _lib.KindInfo:
@@ -70,7 +73,7 @@ class Engine:
     """N instances of one effect kind on one GPU (see module docstring)."""
 
     def __init__(self, kind, n_inst: int, sample_rate: float = 48000.0, block: int = 256,
-                 device: int = 0):
+                 device: int = 0, voices: Optional[int] = None):
         self.lib = load()
         self.kind = KIND_NAMES[kind] if isinstance(kind, str) else int(kind)
         self.n = int(n_inst)
@@ -79,8 +82,15 @@ class Engine:
         self.device = int(device)
         self.info = kind_info(self.kind, sample_rate)
         h = ctypes.c_void_p()
-        check(self.lib.olfx_create(self.kind, self.device, self.n, self.sample_rate, self.block,
-                                   ctypes.byref(h)))
+        if voices is not None:
+            # voices per instrument: the synth only (olfx_create_synth; olfx_create gives the firmware's 4)
+            if self.kind != _lib.KIND_SYNTH:
+                raise ValueError("voices= is for the synth kind")
+            check(self.lib.olfx_create_synth(self.device, self.n, int(voices), self.sample_rate, self.block,
+                                             ctypes.byref(h)))
+        else:
+            check(self.lib.olfx_create(self.kind, self.device, self.n, self.sample_rate, self.block,
+                                       ctypes.byref(h)))
         self._h = h
 
     # ---- lifetime ----
@@ -206,6 +216,19 @@ class Engine:
             arr[k].value = float(e[2])
             arr[k].source = _lib.CTL_HARDWARE if len(e) > 3 and e[3] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
         check(self.lib.olfx_control(self._h, arr, len(evs)), self._h)
+
+    # ---- the synth's Polyvoice (OLFX_KIND_SYNTH) ----
+    @property
+    def voices(self) -> int:
+        """Voices per instrument (0 for other kinds)."""
+        return int(self.lib.olfx_synth_voices(self._h))
+
+    def playing(self, inst: int) -> list:
+        """Playing() of each voice of instrument inst (the last NoteOn's note, 0 after NoteOff), as of
+        the calls made so far (olfx_synth_playing)."""
+        buf = (ctypes.c_uint8 * max(1, self.voices))()
+        check(self.lib.olfx_synth_playing(self._h, int(inst), buf), self._h)
+        return [int(v) for v in buf[:self.voices]]
 
     # ---- processing ----
     def process(self, x, out=None, n_frames: Optional[int] = None, stream=None):
@@ -367,6 +390,19 @@ def control_map(kind, control: int, value: float, source: str = "midi"):
         return "update_only", val.value
     return PARAMS[k][field.value], val.value
 
+def synth_control_map(control: int, value: float, source: str = "midi"):
+    """The synth's control fan-out (the firmware's handleMidi: voices, delay_fx, reverb_fx, filter_fx)
+    for one control change: a list of (field name or "update_only", mapped value), 0..2 entries
+    (olfx_synth_control_map; host-only)."""
+    lib = load()
+    fields = (ctypes.c_uint32 * 2)()
+    vals = (ctypes.c_float * 2)()
+    src = _lib.CTL_HARDWARE if source in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
+    rc = lib.olfx_synth_control_map(int(control), src, float(value), fields, vals)
+    if rc < 0:
+        check(rc, None)
+    names = PARAMS[_lib.KIND_SYNTH]
+    return [("update_only" if fields[k] == _lib.FIELD_UPDATE_ONLY else names[fields[k]], vals[k]) for k in range(rc)]
 
 
 class Polyvoice:

@@ -40,6 +40,8 @@ RANGES["dattorro_rpd"] = [(0, 1)] + RANGES["dattorro"][1:]
 RANGES["chain_rpd"] = RANGES["chorus"] + RANGES["pitchshift"] + RANGES["dattorro_rpd"]
 # the plate rack: the rack's fields, then the plate's (per-instance pre-delays: its ring is in rows)
 RANGES["platerack"] = RANGES["fxrack"] + RANGES["dattorro_rpd"]
+# the synth: the voices' fields, then the rack's with the topology fixed at 1 (the firmware's callback)
+RANGES["synth"] = RANGES["voice"] + RANGES["fxrack"][:-1] + [1.0]
 
 
 def _splitmix64(z: np.ndarray) -> np.ndarray:

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""The synth's fused kernel against the three launches it replaces.
+
+  fused:    one OLFX_KIND_SYNTH engine (synth_block_v1), one launch per block;
+  composed: an OLFX_KIND_VOICE_MOOG engine of instances x voices voices (voice_block_v4), olfx_mix into
+            one bus per instrument (voice_mix), an OLFX_KIND_FXRACK engine at topology 1
+            (fxrack_block_v3): three launches per block, every voice sample and every bus sample
+            through HBM (8 voices + 8 B per instrument-frame).
+Both get the same per-instrument parameters (workload.RANGES["synth"]) and every voice a NoteOn before
+the first block.  Device events around `--steps` blocks per window; at least 50 warm-up launches of
+each path; `--reps` windows per path, the order of the two paths rotated from one repetition to the
+next, in one process.  Prints one JSON line (medians, min-max, the verdict by the rule below, and
+whether the two paths' last blocks -- the same block of the same stream -- agree bit for bit).
+
+The verdict: "faster" only if the fused median lies below the composed median by more than the
+larger of the two min-max spreads; "slower" by the same rule the other way; else "tie".
+
+  python tools/synth_ab.py [--instances 16384] [--voices 4] [--block 256] [--steps 50] [--reps 7]
+  python tools/synth_ab.py --only fused --steps 10      # untimed, for a rocprofv3 --pmc run
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--instances", type=int, default=16384)
+    ap.add_argument("--voices", type=int, default=4)
+    ap.add_argument("--block", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--only", choices=["fused", "composed"], help="run one path untimed (profiler runs)")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    import ol_dsp_amd as ofx
+    from ol_dsp_amd import workload
+    if not torch.cuda.is_available():
+        sys.exit("synth_ab: no GPU (there is no CPU path to time)")
+    dev = torch.device("cuda:0")
+    n, P, B = args.instances, args.voices, args.block
+    p = workload.instance_params("synth", 0, n)
+    nv = len(ofx.PARAMS[ofx.KIND_VOICE])
+    notes = workload.voice_notes(0, n * P).reshape(n, P)
+    out = torch.empty((2, B, n), device=dev)
+    out_c = torch.empty((2, B, n), device=dev)
+
+    paths = {}
+    if args.only != "composed":
+        fused = ofx.Engine("synth", n, block=B, voices=P)
+        fused.set_params(0, p)
+        for q in range(P):                                   # voice q of every instrument
+            fused.note_events(ofx.Engine.make_events(np.arange(n), 1, notes[:, q]))
+        paths["fused"] = lambda k: fused.process(None, out=out)
+    if args.only != "fused":
+        voice, rack = ofx.Engine("voice_moog", n * P, block=B), ofx.Engine("fxrack", n, block=B)
+        # voice i * P + q is voice q of instrument i: contiguous buses, the mix's fastest path (float4 runs)
+        voice.set_params(0, np.repeat(p[:nv], P, axis=1))
+        rack.set_params(0, p[nv:])
+        voice.mix_config([[i * P + q for q in range(P)] for i in range(n)])
+        voice.note_events(ofx.Engine.make_events(np.arange(n * P), 1, notes.reshape(-1)))
+        vo = torch.empty((1, B, n * P), device=dev)
+        x = torch.zeros((2, B, n), device=dev)
+
+        def composed(k):
+            voice.process(None, out=vo)
+            x[0].zero_()                                     # the caller zeroes its frame (Polyvoice.h:28-33)
+            voice.mix(vo, x[0])
+            rack.process(x, out=out_c)
+        paths["composed"] = composed
+
+    def window(run, steps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for k in range(steps):
+            run(k)
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3 / steps           # us per block
+
+    for run in paths.values():
+        window(run, max(args.warmup, 50 if not args.only else 2))
+    if args.only:
+        window(paths[args.only], args.steps)
+        print(json.dumps({"only": args.only, "instances": n, "voices": P, "block": B, "steps": args.steps}))
+        return
+    names = list(paths)
+    us = {name: [] for name in names}
+    for r in range(args.reps):
+        for name in names[r % 2:] + names[:r % 2]:          # rotated
+            us[name].append(window(paths[name], args.steps))
+    res = {"instances": n, "voices": P, "block": B, "steps": args.steps, "reps": args.reps, "warmup": max(args.warmup, 50),
+           "kernels": {"fused": fused.kernel_name, "composed": [voice.kernel_name, "voice_mix", rack.kernel_name]},
+           "device": torch.cuda.get_device_name(0)}
+    for name, v in us.items():
+        res[name] = {"us_per_block_median": statistics.median(v), "us_per_block_min": min(v),
+                     "us_per_block_max": max(v), "us_per_block": v}
+    mf, mc = res["fused"]["us_per_block_median"], res["composed"]["us_per_block_median"]
+    spread = max(res[k]["us_per_block_max"] - res[k]["us_per_block_min"] for k in names)
+    res["larger_spread_us"] = spread
+    res["fused_over_composed_median"] = mf / mc
+    res["verdict"] = "faster" if mc - mf > spread else ("slower" if mf - mc > spread else "tie")
+    res["fused"]["instrument_frames_per_s"] = n * B / (mf * 1e-6)
+    res["hbm_bytes_per_instrument_frame_removed"] = 8 * P + 8
+    # both paths have run the same number of blocks from the same start: their last blocks must agree
+    # bit for bit at the timed size too
+    torch.cuda.synchronize()
+    res["last_block_bit_identical"] = bool(torch.equal(out.view(torch.int32), out_c.view(torch.int32)))
+    res["last_block_nonzero_finite"] = bool(torch.isfinite(out).all() and (out != 0).any())
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
