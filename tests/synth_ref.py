@@ -119,9 +119,9 @@ class Synth:
 # ---- scripts: what a test does, in order ----
 # ("params", p[28][n]) | ("set", inst, field, value) | ("events", [(inst, type, note), ...]) |
 # ("block", frames) | ("check_playing",)  (GPU side only: Engine.playing against the rule's table)
-def run_ref(script, n: int, voices: int = 4, threads: int = 4):
+def run_ref(script, n: int, voices: int = 4, threads: int = 4, sample_rate: float = 48000.0):
     """The composed reference of a script: ([2][frames][n], the Synth)."""
-    ref = Synth(n, voices)
+    ref = Synth(n, voices, sample_rate)
     ref.trace = []
     out = []
     for step in script:

@@ -10,6 +10,8 @@ Every comparison is helpers.same_bits_or_nan: +-Inf, +-0 and subnormals exact, t
 NaN sign and payload not compared (x86 and the GPU generate different default NaNs).  Each signal
 also states a condition on the ORACLE's output (a share of subnormal or non-finite samples), so
 that no case passes without the edge it is about; the shares are printed (pytest -s).
+The three fused kinds (platerack, voice_sample, synth) get the same questions in
+tests/test_gpu_edges_fused.py.
 """
 import numpy as np
 import pytest
