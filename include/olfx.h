@@ -87,7 +87,7 @@ enum {
                                   olfx_set_member, olfx_update and the voice buses as OLFX_KIND_VOICE.  GateOn /
                                   NoteOn also Seek(0) and Play() the sample, GateOff / NoteOff Pause() it
                                   (SampleSoundSource.h:21-26); SetFreq only stores the pitch (:28-30). */
-    OLFX_KIND_SYNTH = 11       /* the Daisy synth firmware's audio callback (ol_daisy/app/synth/main.cpp:78-86) in
+    OLFX_KIND_SYNTH = 11,      /* the Daisy synth firmware's audio callback (ol_daisy/app/synth/main.cpp:78-86) in
                                   one launch (synth.hip): per instrument, P MoogFilter SynthVoices behind a
                                   Polyvoice (mono = 0; mono += v[0]; ... += v[P-1]) -> DelayFx<1> -> stereo copy
                                   -> ReverbFx<2> over the ReverbSc stub -> FilterFx<2> in place.  No input;
@@ -96,6 +96,16 @@ enum {
                                   OLFX_KIND_VOICE_MOOG + olfx_mix + OLFX_KIND_FXRACK at OLFX_FR_TOPOLOGY 1 give
                                   for the sum in input channel 0.  P = 4 (olfx_create) or 1..8
                                   (olfx_create_synth).  OLFX_SY_* fields and rules below. */
+    OLFX_KIND_SYNTH_SVF = 12   /* the library's own voice as a polyphonic instrument, one launch (synth.hip):
+                                  per instrument, P SynthVoice(OscillatorSoundSource, SvfFilter) -- the default-
+                                  constructed SynthVoice, OLFX_KIND_VOICE's -- behind a Polyvoice, into the rack
+                                  at the instrument's OLFX_FR_TOPOLOGY: 1 as OLFX_KIND_SYNTH, or 0,
+                                  FxRack<2>::Process (Fx.h:432-440) with its master volume on the frame
+                                  (mono, 0.0f), the path SynthEngine::Process (app/synth/SynthEngine.h:24-32)
+                                  hands the voice sum to.  No input; out [2][n_frames][n_inst] -- bit for bit what
+                                  OLFX_KIND_VOICE + olfx_mix + OLFX_KIND_FXRACK at that topology give for the sum
+                                  in input channel 0 and zeros in channel 1.  P = 4 (olfx_create) or 1..8
+                                  (olfx_create_synth_kind).  OLFX_SY_* fields; rules below. */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -229,7 +239,22 @@ enum {
    the same route through the UpdateHardwareControl handlers.  olfx_synth_control_map gives the fields hit;
    olfx_control_map(OLFX_KIND_SYNTH, ...) returns OLFX_E_KIND (it has one field to give).
    Refused on this kind, with the code each call uses for a wrong kind (OLFX_E_STATE): olfx_mix_config and
-   olfx_mix (there are no buses: the sum never leaves the kernel), olfx_sample_bank, olfx_sample_voices. */
+   olfx_mix (there are no buses: the sum never leaves the kernel), olfx_sample_bank, olfx_sample_voices.
+
+   Svf synth (OLFX_KIND_SYNTH_SVF): the same 28 fields in the same layout and every rule above, except:
+     OLFX_SY_VOICE0 + OLFX_VC_* defaults and validation as OLFX_KIND_VOICE; FILTER_DRIVE is live (SvfFilter::SetDrive)
+     OLFX_SY_RACK0 + OLFX_FR_*  as OLFX_KIND_FXRACK, but TOPOLOGY defaults to 1 and accepts 0 or 1 (else
+                                OLFX_E_ARG, nothing changes), per instrument -- one engine may mix both, and a
+                                change lands at the next block boundary like every parameter change;
+                                MASTER_VOLUME is live at topology 0, stored and ignored at topology 1
+   Topology 0: DelayFx<2> -> ReverbFx<2> over the stub -> filter1 into the zeroed buf_c -> x master: out 0 =
+   c0 * master, out 1 = 0.0f * master.  Channel 1's delay line reaches no output at either topology; its
+   contents are unspecified.
+   Controls: olfx_control sends the event to the voices (SynthVoice's mapping as OLFX_KIND_VOICE has it, every
+   voice), then to the rack with the mapping olfx_control uses on an OLFX_KIND_FXRACK instance of the
+   instrument's current topology: at 1 the firmware's direct routing (CCs 41-44 hit both filters), at 0
+   FxRack::UpdateMidiControl / UpdateHardwareControl (CCs 45-48 drive FILTER_*, CC 7 the master volume).
+   olfx_synth_control_map_at gives the fields hit; olfx_control_map(OLFX_KIND_SYNTH_SVF, ...) is OLFX_E_KIND. */
 #define OLFX_SY_VOICE0    0
 #define OLFX_SY_RACK0     (OLFX_VC_NPARAMS)
 #define OLFX_SY_NPARAMS   (OLFX_VC_NPARAMS + OLFX_FR_NPARAMS)
@@ -314,6 +339,9 @@ int olfx_create(int kind, int device, uint32_t n_inst, float sample_rate, uint32
    olfx_create(OLFX_KIND_SYNTH, ...) is the firmware's 4. */
 int olfx_create_synth(int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
                       olfx_engine **out);
+/* The same for either synth kind: kind is OLFX_KIND_SYNTH or OLFX_KIND_SYNTH_SVF (else OLFX_E_KIND). */
+int olfx_create_synth_kind(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                           olfx_engine **out);
 int olfx_destroy(olfx_engine *e);
 
 /* Zero all state and restore defaults (== destroy + create, without reallocating).  Like
@@ -350,13 +378,20 @@ int olfx_get_param(olfx_engine *e, uint32_t inst, uint32_t field, float *value);
 
 /* Map one control change to (field, value) exactly as the reference handler scales it
    (ol::core::scale, corelib/ol_corelib.h:31-44).  Returns OLFX_OK, OLFX_IGNORED, or an error.
-   Pure host function: no engine, no device.  OLFX_KIND_SYNTH: OLFX_E_KIND -- a control can hit two of its
-   fields, see olfx_synth_control_map. */
+   Pure host function: no engine, no device.  OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF: OLFX_E_KIND -- a control
+   can hit two of their fields, see olfx_synth_control_map / olfx_synth_control_map_at. */
 int olfx_control_map(int kind, uint8_t control, int source, float value, uint32_t *field, float *param_value);
 /* The same for an OLFX_KIND_SYNTH instrument (the firmware's handleMidi fan-out, main.cpp:201-207): the
    voices' mapping first (OLFX_SY_VOICE0 + ..., or OLFX_FIELD_UPDATE_ONLY), then the rack's topology-1
    mapping (OLFX_SY_RACK0 + ...).  Returns the number of fields hit (0..2) or an error.  Pure host function. */
 int olfx_synth_control_map(uint8_t control, int source, float value, uint32_t field[2], float param_value[2]);
+/* The same for either synth kind at a rack topology: the voices' mapping of that kind, then the mapping
+   olfx_control uses on an OLFX_KIND_FXRACK instance of that topology (0: FxRack's handlers, 1: the firmware's
+   direct routing).  kind OLFX_KIND_SYNTH at topology 1 equals olfx_synth_control_map; OLFX_E_ARG for a topology
+   the kind does not accept (OLFX_KIND_SYNTH: anything but 1; OLFX_KIND_SYNTH_SVF: anything but 0 or 1),
+   OLFX_E_KIND for another kind.  Pure host function. */
+int olfx_synth_control_map_at(int kind, uint32_t topology, uint8_t control, int source, float value, uint32_t field[2],
+                              float param_value[2]);
 /* Apply control changes in order (each: the mapped olfx_set_param; ignored controls skipped).
    Replaces UpdateMidiControl / UpdateHardwareControl per instance. */
 int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
@@ -365,7 +400,7 @@ int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
 int olfx_note_events(olfx_engine *e, const olfx_event *ev, uint32_t n);
 /* The same queue with SET_FREQUENCY (Voice::SetFrequency, SynthVoice.h:264-267) as well. */
 int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n);
-/* OLFX_KIND_SYNTH: Playing() of the `voices` voices of instrument inst, as of the calls made so far. */
+/* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF: Playing() of the `voices` voices of instrument inst, as of the calls made so far. */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);
 
 /* Update() of instances [first, first + count) with their current parameters (SynthVoice.h:66-98,
@@ -438,7 +473,7 @@ uint32_t olfx_num_instances(const olfx_engine *e);
 int      olfx_kind(const olfx_engine *e);
 uint64_t olfx_frames_processed(const olfx_engine *e);   /* per instance, since create/reset */
 uint32_t olfx_num_buses(const olfx_engine *e);          /* voice buses (olfx_mix_config) */
-uint32_t olfx_synth_voices(const olfx_engine *e);       /* voices per instrument (OLFX_KIND_SYNTH), else 0 */
+uint32_t olfx_synth_voices(const olfx_engine *e);       /* voices per instrument (the synth kinds), else 0 */
 /* Algorithmic ("compulsory") HBM bytes per instance-frame of the dominant kernel, the figure
    bench.py's roofline uses. */
 double   olfx_algorithmic_bytes_per_frame(const olfx_engine *e);

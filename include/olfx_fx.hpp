@@ -226,8 +226,11 @@ public:
    UpdateHardwareControl are handleMidi's fan-out to the voices and the three effects (:201-207). */
 class SynthBank : public Engine {
 public:
-    SynthBank(uint32_t n_inst, float sample_rate, uint32_t voices = 4, uint32_t block = 256, int device = 0)
-        : Engine(make(n_inst, sample_rate, voices, block, device)) {}
+    /* kind: OLFX_KIND_SYNTH (MoogFilter voices, the firmware) or OLFX_KIND_SYNTH_SVF (SvfFilter voices; the
+       rack at topology 0 or 1 per instrument) */
+    SynthBank(uint32_t n_inst, float sample_rate, uint32_t voices = 4, uint32_t block = 256, int device = 0,
+              int kind = OLFX_KIND_SYNTH)
+        : Engine(make(kind, n_inst, sample_rate, voices, block, device)) {}
     uint32_t voices() const { return olfx_synth_voices(e_); }
     /* Polyvoice::UpdateConfig + Update: every voice of the instrument */
     void UpdateConfig(uint32_t i, const float config[OLFX_VC_NPARAMS]) {
@@ -256,9 +259,10 @@ public:
     }
 
 private:
-    static olfx_engine *make(uint32_t n_inst, float sample_rate, uint32_t voices, uint32_t block, int device) {
+    static olfx_engine *make(int kind, uint32_t n_inst, float sample_rate, uint32_t voices, uint32_t block, int device) {
         olfx_engine *e = nullptr;
-        check(olfx_create_synth(device, n_inst, voices, sample_rate, block, &e), nullptr, "olfx_create_synth");
+        check(olfx_create_synth_kind(kind, device, n_inst, voices, sample_rate, block, &e), nullptr,
+              "olfx_create_synth_kind");
         return e;
     }
     void push(uint32_t i, uint8_t type, uint8_t note, uint8_t vel) {

@@ -33,6 +33,7 @@ KIND_VOICE_MOOG = 7
 KIND_PLATERACK = 8
 KIND_VOICE_SAMPLE = 10      # 9 is unassigned (olfx.h)
 KIND_SYNTH = 11
+KIND_SYNTH_SVF = 12
 
 NO_SAMPLE = 0xFFFFFFFF
 SAMPLE_ONESHOT = 0
@@ -120,6 +121,7 @@ SIGNATURES = {
     "olfx_kind_info_get": (ctypes.c_int, [ctypes.c_int, _F, ctypes.POINTER(KindInfo)]),
     "olfx_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_create_synth": (ctypes.c_int, [ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
+    "olfx_create_synth_kind": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_destroy": (ctypes.c_int, [_P]),
     "olfx_reset": (ctypes.c_int, [_P]),
     "olfx_set_params": (ctypes.c_int, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(_F)]),
@@ -134,6 +136,8 @@ SIGNATURES = {
                                         ctypes.POINTER(_F)]),
     "olfx_synth_control_map": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
                                               ctypes.POINTER(_F)]),
+    "olfx_synth_control_map_at": (ctypes.c_int, [ctypes.c_int, _U32, ctypes.c_uint8, ctypes.c_int, _F,
+                                                 ctypes.POINTER(_U32), ctypes.POINTER(_F)]),
     "olfx_control": (ctypes.c_int, [_P, ctypes.POINTER(ControlEvent), _U32]),
     "olfx_process": (ctypes.c_int, [_P, _P, _P, _U32, ctypes.c_int, _P]),
     "olfx_sync": (ctypes.c_int, [_P]),

@@ -186,7 +186,7 @@ size_t carve(olfx_engine *e, char *base) {
     };
     const int kind = e->kind;
     const size_t n = e->n, nd = e->n_dt;
-    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK || kind == OLFX_KIND_SYNTH) {
+    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK || is_synth_kind(kind)) {
         take(e->fr_ring, (size_t)kFrMaxDelay * 2 * n * 4);
         take(e->fr_state, (size_t)FRS_N * n * 4);
         take(e->fr_coef, (size_t)FRC_N * n * 4);
@@ -213,9 +213,9 @@ size_t carve(olfx_engine *e, char *base) {
         take(e->vc_coef, (size_t)VCC_N * n * 4);
     }
     if (kind == OLFX_KIND_VOICE_SAMPLE) take(e->sm_asg, (size_t)SMC_N * n * 4);
-    if (kind == OLFX_KIND_SYNTH) {
+    if (is_synth_kind(kind)) {
         // every voice slot's state (voices x n rounded up to 64); one set of coefficients per instrument
-        take(e->vc_state, (size_t)VCS_N_MOOG * e->hs.n_ev() * 4);
+        take(e->vc_state, (size_t)voice_state_slots(kind) * e->hs.n_ev() * 4);
         take(e->vc_coef, (size_t)VCC_N * n * 4);
     }
     return off;
@@ -246,7 +246,8 @@ uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: dst[0] = e->vc_coef; break;
     case OLFX_KIND_VOICE_SAMPLE: dst[0] = e->vc_coef; dst[1] = e->sm_asg; break;
-    case OLFX_KIND_SYNTH: dst[0] = e->vc_coef; dst[1] = e->fr_coef; break;
+    case OLFX_KIND_SYNTH:
+    case OLFX_KIND_SYNTH_SVF: dst[0] = e->vc_coef; dst[1] = e->fr_coef; break;
     default: break;
     }
     a->nseg = sg.nseg;
@@ -577,7 +578,8 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_platerack(a, s);
         break;
     }
-    case OLFX_KIND_SYNTH: {
+    case OLFX_KIND_SYNTH:
+    case OLFX_KIND_SYNTH_SVF: {
         // one fused launch: the voice waves feed the delay waves and the filter wave through LDS
         SynthArgs a{};
         a.ring = e->fr_ring;
@@ -594,6 +596,7 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.npad = e->hs.npad;
         a.ev = ev.ev;
         a.ev_more = ev.ev_more;
+        a.svf = e->kind == OLFX_KIND_SYNTH_SVF;
         r = launch_synth(a, s);
         break;
     }
@@ -719,6 +722,21 @@ int olfx_create_synth(int device, uint32_t n_inst, uint32_t voices, float sample
     return create_engine(OLFX_KIND_SYNTH, device, n_inst, voices, sample_rate, block, out);
 }
 
+int olfx_create_synth_kind(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
+                           olfx_engine **out) {
+    if (!out) return OLFX_E_ARG;
+    *out = nullptr;
+    if (!is_synth_kind(kind)) {
+        set_global_error("olfx_create_synth_kind: kind %d is not a synth", kind);
+        return OLFX_E_KIND;
+    }
+    if (voices < 1 || voices > host::kSynthMaxVoices) {
+        set_global_error("olfx_create_synth_kind: %u voices per instrument (1..%u)", voices, host::kSynthMaxVoices);
+        return OLFX_E_ARG;
+    }
+    return create_engine(kind, device, n_inst, voices, sample_rate, block, out);
+}
+
 static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
                          olfx_engine **out) {
     if (!out) return OLFX_E_ARG;
@@ -728,7 +746,7 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
         return OLFX_E_KIND;
     }
     // (the synth's voice slots, voices x n rounded up to 64, are indexed in 32 bits)
-    const bool too_many = kind == OLFX_KIND_SYNTH && ((uint64_t)n_inst + 63u) / 64u * 64u * voices > 0x7FFFFFFFull;
+    const bool too_many = is_synth_kind(kind) && ((uint64_t)n_inst + 63u) / 64u * 64u * voices > 0x7FFFFFFFull;
     if (n_inst == 0 || too_many || !(sample_rate > 1000.f && sample_rate <= 384000.f) || block == 0 || (block & 3u)) {
         set_global_error("olfx_create: bad argument (n_inst=%u sr=%g block=%u)", n_inst, sample_rate, block);
         return OLFX_E_ARG;
@@ -1111,6 +1129,7 @@ const char *olfx_kernel_name(const olfx_engine *e) {
     case OLFX_KIND_FXRACK: return "fxrack_block_v3";
     case OLFX_KIND_PLATERACK: return "platerack_block_v1";
     case OLFX_KIND_SYNTH: return "synth_block_v1";
+    case OLFX_KIND_SYNTH_SVF: return "synth_svf_block_v1";
     default: return "";
     }
 }

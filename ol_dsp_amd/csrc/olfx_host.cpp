@@ -57,12 +57,13 @@ uint32_t n_params_of(int kind) {
     case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
     case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
     case OLFX_KIND_PLATERACK: return OLFX_PR_NPARAMS;
-    case OLFX_KIND_SYNTH: return OLFX_SY_NPARAMS;
+    case OLFX_KIND_SYNTH:
+    case OLFX_KIND_SYNTH_SVF: return OLFX_SY_NPARAMS;
     default: return 0;
     }
 }
 
-uint32_t in_channels(int kind) { return is_voice_kind(kind) || kind == OLFX_KIND_SYNTH ? 0u : 2u; }
+uint32_t in_channels(int kind) { return is_voice_kind(kind) || is_synth_kind(kind) ? 0u : 2u; }
 uint32_t out_channels(int kind) { return is_voice_kind(kind) ? 1u : 2u; }
 
 // ol::core::scale (modules/corelib/ol_corelib.h:27-44), t_sample = float
@@ -163,6 +164,12 @@ void default_params(int kind, float *p) {
         default_params(OLFX_KIND_FXRACK, p + OLFX_SY_RACK0);
         p[OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY] = 1.f;
         break;
+    case OLFX_KIND_SYNTH_SVF:
+        // the library's default-constructed SynthVoice behind the same rack, the firmware's callback first
+        default_params(OLFX_KIND_VOICE, p + OLFX_SY_VOICE0);
+        default_params(OLFX_KIND_FXRACK, p + OLFX_SY_RACK0);
+        p[OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY] = 1.f;
+        break;
     default: break;
     }
 }
@@ -194,6 +201,9 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
     case OLFX_KIND_SYNTH:           // the rack's, one set of voice coefficients, four voices' state
         return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4 + VCC_N * 4 +
                 (uint64_t)kSynthDefaultVoices * VCS_N_MOOG * 4) * n;
+    case OLFX_KIND_SYNTH_SVF:       // the same with OLFX_KIND_VOICE's per-voice state
+        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4 + VCC_N * 4 +
+                (uint64_t)kSynthDefaultVoices * VCS_N * 4) * n;
     default: return 0;
     }
 }
@@ -210,7 +220,8 @@ double algorithmic_bytes_per_frame(int kind) {
     case OLFX_KIND_CHAIN: return 228.6;
     case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
     case OLFX_KIND_PLATERACK: return 32.0 + 164.6 - 16.0;   // rack + plate - the plate's own I/O (in LDS now)
-    case OLFX_KIND_SYNTH: return 32.0 - 8.0;   // the rack at topology 1 with no input read: ring 8 + 8, out 8
+    case OLFX_KIND_SYNTH:                      // the rack at topology 1 with no input read: ring 8 + 8, out 8
+    case OLFX_KIND_SYNTH_SVF: return 32.0 - 8.0;   // (topology 0 stores its zero channel too: the same)
     default: return 0.0;
     }
 }
@@ -228,7 +239,8 @@ double algorithmic_read_bytes_per_frame(int kind) {
     case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
     case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
     case OLFX_KIND_PLATERACK: return 16.0 + 6445.0 * 4.0 / 256.0;   // rack + the plate's taps (its input is in LDS)
-    case OLFX_KIND_SYNTH: return 16.0 - 8.0;   // the ring read; the input never leaves LDS
+    case OLFX_KIND_SYNTH:
+    case OLFX_KIND_SYNTH_SVF: return 16.0 - 8.0;   // the ring read; the input never leaves LDS
     default: return 0.0;
     }
 }
@@ -435,7 +447,8 @@ Segments coef_segments(int kind) {
     case OLFX_KIND_VOICE:
     case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
     case OLFX_KIND_VOICE_SAMPLE: return {2, {VCC_N, SMC_N, 0}};   // the voice, its Sample
-    case OLFX_KIND_SYNTH: return {2, {VCC_N, FRC_N, 0}};          // the instrument's voices, its rack
+    case OLFX_KIND_SYNTH:
+    case OLFX_KIND_SYNTH_SVF: return {2, {VCC_N, FRC_N, 0}};      // the instrument's voices, its rack
     default: return {0, {0, 0, 0}};
     }
 }
@@ -472,7 +485,8 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
         if (kind == OLFX_KIND_VOICE_SAMPLE) sample_record(i, w + VCC_N);
         break;
     case OLFX_KIND_SYNTH:
-        derive_voice(p + OLFX_SY_VOICE0, configured[i] != 0, true, sr, fc);
+    case OLFX_KIND_SYNTH_SVF:
+        derive_voice(p + OLFX_SY_VOICE0, configured[i] != 0, kind == OLFX_KIND_SYNTH, sr, fc);
         std::memcpy(w, fc, VCC_N * 4);
         derive_fxrack(p + OLFX_SY_RACK0, sr, w + VCC_N);
         break;
@@ -533,6 +547,9 @@ const char *Shadow::bad_value(uint32_t field, float v) const {
     // the firmware's callback is the only chain the synth kernel runs
     if (kind == OLFX_KIND_SYNTH && field == OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY && v != 1.f)
         return "synth rack topology must be 1";
+    // the Svf synth runs the rack proper (0) as well; the components alone (2..4) have no voices in front
+    if (kind == OLFX_KIND_SYNTH_SVF && field == OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY && !(v == 0.f || v == 1.f))
+        return "svf synth rack topology must be 0 or 1";
     return nullptr;
 }
 
@@ -708,11 +725,14 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
-        if (kind == OLFX_KIND_SYNTH) {
-            // handleMidi (main.cpp:201-207): the voices, then delay_fx, reverb_fx, filter_fx
+        if (is_synth_kind(kind)) {
+            // handleMidi (main.cpp:201-207): the voices, then delay_fx, reverb_fx, filter_fx; the Svf synth at
+            // topology 0: the voices, then FxRack's own handlers
             uint32_t fields[2];
             float vals[2];
-            const int hits = olfx_synth_control_map(ev[k].control, ev[k].source, ev[k].value, fields, vals);
+            const float tp = params[(size_t)(OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY) * n + ev[k].inst];
+            const int hits = olfx_synth_control_map_at(kind, (uint32_t)tp, ev[k].control, ev[k].source, ev[k].value,
+                                                       fields, vals);
             if (hits < 0) return fail(hits, "olfx_control: event %u", k);
             for (int h = 0; h < hits; ++h) {
                 if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {    // the voices' Update() with unchanged members
@@ -767,7 +787,7 @@ int Shadow::note_events(const olfx_event *ev, uint32_t count) {
             return fail(OLFX_E_ARG, "olfx_note_events: bad event %u", k);
     }
     for (uint32_t k = 0; k < count; ++k) {
-        if (kind == OLFX_KIND_SYNTH) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        if (is_synth_kind(kind)) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         else events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
     }
     return OLFX_OK;
@@ -781,7 +801,7 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
             (ev[k].type == OLFX_EV_SET_FREQUENCY && !std::isfinite(ev[k].value)))
             return fail(OLFX_E_ARG, "olfx_voice_events: bad event %u", k);
     }
-    if (kind == OLFX_KIND_SYNTH) {
+    if (is_synth_kind(kind)) {
         for (uint32_t k = 0; k < count; ++k) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         return OLFX_OK;
     }
@@ -825,7 +845,7 @@ void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velo
 }
 
 int Shadow::synth_playing(uint32_t inst, uint8_t *out) {
-    if (kind != OLFX_KIND_SYNTH) return fail(OLFX_E_STATE, "olfx_synth_playing: not a synth engine");
+    if (!is_synth_kind(kind)) return fail(OLFX_E_STATE, "olfx_synth_playing: not a synth engine");
     if (inst >= n || !out) return fail(OLFX_E_ARG, "olfx_synth_playing: bad argument");
     for (uint32_t p = 0; p < voices; ++p) out[p] = playing[(size_t)p * n + inst];
     return OLFX_OK;
@@ -1023,20 +1043,31 @@ extern "C" int olfx_control_map(int kind, uint8_t control, int source, float val
         default: return OLFX_IGNORED;              // incl. the reverb CCs that reach only the ReverbSc stub
         }
     }
-    // the synth's controls can hit two fields: olfx_synth_control_map
-    return n_params_of(kind) && kind != OLFX_KIND_SYNTH ? OLFX_IGNORED : OLFX_E_KIND;
+    // the synths' controls can hit two fields: olfx_synth_control_map / olfx_synth_control_map_at
+    return n_params_of(kind) && !is_synth_kind(kind) ? OLFX_IGNORED : OLFX_E_KIND;
 }
 
 // handleMidi's fan-out (main.cpp:201-207), from the two kinds' tables above: the voices' handler, then
 // the rack's at topology 1 as Shadow::control routes it (DelayFx 35-39, ReverbFx's balance 34 -- its
 // other controls reach only the ReverbSc stub --, FilterFx 41-44 through the rack's 45-48 entries)
 extern "C" int olfx_synth_control_map(uint8_t control, int source, float value, uint32_t field[2], float param_value[2]) {
+    return olfx_synth_control_map_at(OLFX_KIND_SYNTH, 1u, control, source, value, field, param_value);
+}
+
+// The same for either synth kind at a rack topology: the kind's voice table, then the rack's as
+// Shadow::control routes an OLFX_KIND_FXRACK instance of that topology -- 1 as above, 0 FxRack's own
+// UpdateMidiControl / UpdateHardwareControl (the rack's table as it stands: 45-48 the filter, 7 the master)
+extern "C" int olfx_synth_control_map_at(int kind, uint32_t topology, uint8_t control, int source, float value,
+                                         uint32_t field[2], float param_value[2]) {
+    using namespace olfx;
     using namespace olfx::host;
+    if (!is_synth_kind(kind)) return OLFX_E_KIND;
     if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
+    if (topology > 1u || (kind == OLFX_KIND_SYNTH && topology != 1u)) return OLFX_E_ARG;
     int hits = 0;
     uint32_t f;
     float v;
-    int rc = olfx_control_map(OLFX_KIND_VOICE_MOOG, control, source, value, &f, &v);
+    int rc = olfx_control_map(kind == OLFX_KIND_SYNTH ? OLFX_KIND_VOICE_MOOG : OLFX_KIND_VOICE, control, source, value, &f, &v);
     if (rc < 0) return rc;
     if (rc == OLFX_OK) {
         field[hits] = f == OLFX_FIELD_UPDATE_ONLY ? f : OLFX_SY_VOICE0 + f;
@@ -1044,8 +1075,8 @@ extern "C" int olfx_synth_control_map(uint8_t control, int source, float value, 
     }
     const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
     const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
-    if (filter_cc || delay_cc || control == CC_REVERB_BALANCE) {
-        const uint8_t as = filter_cc ? (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF) : control;
+    if (topology == 0u || filter_cc || delay_cc || control == CC_REVERB_BALANCE) {
+        const uint8_t as = topology == 1u && filter_cc ? (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF) : control;
         rc = olfx_control_map(OLFX_KIND_FXRACK, as, source, value, &f, &v);
         if (rc < 0) return rc;
         if (rc == OLFX_OK) {

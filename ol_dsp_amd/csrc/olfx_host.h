@@ -21,9 +21,9 @@ uint32_t in_channels(int kind);
 uint32_t out_channels(int kind);
 void default_params(int kind, float *p);     // the reference's defaults of the user-facing parameters
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize);
-uint64_t state_bytes(int kind, uint32_t n, float sr);      // OLFX_KIND_SYNTH: the 4-voice figure
+uint64_t state_bytes(int kind, uint32_t n, float sr);      // the synth kinds: the 4-voice figure
 // kinds that take note events (the voices, and the synth through its Polyvoice router)
-inline bool takes_note_events(int kind) { return is_voice_kind(kind) || kind == OLFX_KIND_SYNTH; }
+inline bool takes_note_events(int kind) { return is_voice_kind(kind) || is_synth_kind(kind); }
 constexpr uint32_t kSynthDefaultVoices = 4, kSynthMaxVoices = 8;
 double algorithmic_bytes_per_frame(int kind);
 double algorithmic_read_bytes_per_frame(int kind);
@@ -109,11 +109,11 @@ struct Shadow {
     void init(int kind_, uint32_t n_, float sr_, uint32_t voices_ = kSynthDefaultVoices) {
         kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_);
         samples.assign(kind_ == OLFX_KIND_VOICE_SAMPLE ? n_ : 0u, SampleAsg{});
-        voices = kind_ == OLFX_KIND_SYNTH ? voices_ : 0u;
-        npad = kind_ == OLFX_KIND_SYNTH ? (n_ + 63u) & ~63u : 0u;
+        voices = is_synth_kind(kind_) ? voices_ : 0u;
+        npad = is_synth_kind(kind_) ? (n_ + 63u) & ~63u : 0u;
     }
     // the voice slots that note events address: the instances themselves, or the synth's voices
-    uint32_t n_ev() const { return kind == OLFX_KIND_SYNTH ? voices * npad : n; }
+    uint32_t n_ev() const { return is_synth_kind(kind) ? voices * npad : n; }
     // Every instance at the reference's defaults, unconfigured, all dirty; nothing queued.
     void reset();
 
@@ -156,7 +156,7 @@ private:
     void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
-        return is_voice_kind(kind) || (kind == OLFX_KIND_SYNTH && n_fields && field0 < OLFX_SY_RACK0);
+        return is_voice_kind(kind) || (is_synth_kind(kind) && n_fields && field0 < OLFX_SY_RACK0);
     }
 };
 

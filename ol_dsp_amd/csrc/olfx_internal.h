@@ -298,11 +298,13 @@ hipError_t launch_platerack(const PlateRackArgs &a, hipStream_t s);
 // planes and the event slots (npad = n rounded up to 64: a 64-voice group is one voice slot of 64
 // consecutive instruments); the voice coefficients are the instrument's ([VCC_N][n]: Polyvoice fans
 // every setter out to all its voices).
+// svf = 1 (OLFX_KIND_SYNTH_SVF): SvfFilter voices (state planes [VCS_N]) and the rack at each instrument's
+// topology, 0 or 1 (FRC_TOPO).
 struct SynthArgs {
     float *ring;                // [n][kFrMaxDelay][2]
     uint32_t *fr_state;         // [FRS_N][n]
     const uint32_t *fr_coef;    // [FRC_N][n]
-    float *vc_state;            // [VCS_N_MOOG][voices * npad]
+    float *vc_state;            // [VCS_N_MOOG][voices * npad]; svf: [VCS_N][voices * npad]
     const float *vc_coef;       // [VCC_N][n]
     float *out;                 // [2][..][n]
     uint64_t plane;
@@ -311,6 +313,7 @@ struct SynthArgs {
     uint32_t voices, npad;
     const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
     const uint2 *ev_more;
+    uint32_t svf;               // 1: synth_svf_block_v1
 };
 hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
 

@@ -115,7 +115,11 @@ enum {
 inline bool is_voice_kind(int k) {
     return k == OLFX_KIND_VOICE || k == OLFX_KIND_VOICE_MOOG || k == OLFX_KIND_VOICE_SAMPLE;
 }
-inline uint32_t voice_state_slots(int k) { return k == OLFX_KIND_VOICE_MOOG ? (uint32_t)VCS_N_MOOG : (uint32_t)VCS_N; }
+inline bool is_synth_kind(int k) { return k == OLFX_KIND_SYNTH || k == OLFX_KIND_SYNTH_SVF; }
+// (a synth's voices: the Moog synth's are MoogFilter voices, the Svf synth's SvfFilter voices)
+inline uint32_t voice_state_slots(int k) {
+    return k == OLFX_KIND_VOICE_MOOG || k == OLFX_KIND_SYNTH ? (uint32_t)VCS_N_MOOG : (uint32_t)VCS_N;
+}
 
 // Note events of one block, folded per voice on the host (olfx_host.cpp fold_events) and applied
 // by the voice kernel itself as its first act on the voice's state (SynthVoice.h:231-268: the

@@ -32,6 +32,7 @@ KIND_NAMES = {
     "platerack": _lib.KIND_PLATERACK,
     "voice_sample": _lib.KIND_VOICE_SAMPLE,
     "synth": _lib.KIND_SYNTH,
+    "synth_svf": _lib.KIND_SYNTH_SVF,
 }
 
 # parameter field names, in C-ABI order
@@ -57,6 +58,7 @@ PARAMS[_lib.KIND_CHAIN] = (["chorus_" + p for p in PARAMS[_lib.KIND_CHORUS]]
 PARAMS[_lib.KIND_PLATERACK] = PARAMS[_lib.KIND_FXRACK] + ["verb_" + p for p in PARAMS[_lib.KIND_DATTORRO]]
 # the synth: the voices' fields, then the rack's (OLFX_SY_*; the two lists share filter_cutoff and others)
 PARAMS[_lib.KIND_SYNTH] = PARAMS[_lib.KIND_VOICE] + ["rack_" + p for p in PARAMS[_lib.KIND_FXRACK]]
+PARAMS[_lib.KIND_SYNTH_SVF] = PARAMS[_lib.KIND_SYNTH]
 
 
 def kind_info(kind: int, sample_rate: float = 48000.0) -> _lib.KindInfo:
@@ -83,11 +85,11 @@ class Engine:
         self.info = kind_info(self.kind, sample_rate)
         h = ctypes.c_void_p()
         if voices is not None:
-            # voices per instrument: the synth only (olfx_create_synth; olfx_create gives the firmware's 4)
-            if self.kind != _lib.KIND_SYNTH:
-                raise ValueError("voices= is for the synth kind")
-            check(self.lib.olfx_create_synth(self.device, self.n, int(voices), self.sample_rate, self.block,
-                                             ctypes.byref(h)))
+            # voices per instrument: the synth kinds only (olfx_create_synth_kind; olfx_create gives 4)
+            if self.kind not in (_lib.KIND_SYNTH, _lib.KIND_SYNTH_SVF):
+                raise ValueError("voices= is for the synth kinds")
+            check(self.lib.olfx_create_synth_kind(self.kind, self.device, self.n, int(voices), self.sample_rate,
+                                                  self.block, ctypes.byref(h)))
         else:
             check(self.lib.olfx_create(self.kind, self.device, self.n, self.sample_rate, self.block,
                                        ctypes.byref(h)))
@@ -217,7 +219,7 @@ class Engine:
             arr[k].source = _lib.CTL_HARDWARE if len(e) > 3 and e[3] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
         check(self.lib.olfx_control(self._h, arr, len(evs)), self._h)
 
-    # ---- the synth's Polyvoice (OLFX_KIND_SYNTH) ----
+    # ---- the synth's Polyvoice (OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF) ----
     @property
     def voices(self) -> int:
         """Voices per instrument (0 for other kinds)."""
@@ -390,15 +392,17 @@ def control_map(kind, control: int, value: float, source: str = "midi"):
         return "update_only", val.value
     return PARAMS[k][field.value], val.value
 
-def synth_control_map(control: int, value: float, source: str = "midi"):
-    """The synth's control fan-out (the firmware's handleMidi: voices, delay_fx, reverb_fx, filter_fx)
-    for one control change: a list of (field name or "update_only", mapped value), 0..2 entries
-    (olfx_synth_control_map; host-only)."""
+def synth_control_map(control: int, value: float, source: str = "midi", kind="synth", topology: int = 1):
+    """A synth kind's control fan-out for one control change at a rack topology: the voices, then the rack
+    as olfx_control routes a rack instance of that topology (1: the firmware's handleMidi -- delay_fx,
+    reverb_fx, filter_fx; 0, the Svf synth only: FxRack's own handlers).  A list of (field name or
+    "update_only", mapped value), 0..2 entries (olfx_synth_control_map_at; host-only)."""
     lib = load()
     fields = (ctypes.c_uint32 * 2)()
     vals = (ctypes.c_float * 2)()
     src = _lib.CTL_HARDWARE if source in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
-    rc = lib.olfx_synth_control_map(int(control), src, float(value), fields, vals)
+    k = KIND_NAMES[kind] if isinstance(kind, str) else int(kind)
+    rc = lib.olfx_synth_control_map_at(k, int(topology), int(control), src, float(value), fields, vals)
     if rc < 0:
         check(rc, None)
     names = PARAMS[_lib.KIND_SYNTH]

@@ -42,6 +42,8 @@ RANGES["chain_rpd"] = RANGES["chorus"] + RANGES["pitchshift"] + RANGES["dattorro
 RANGES["platerack"] = RANGES["fxrack"] + RANGES["dattorro_rpd"]
 # the synth: the voices' fields, then the rack's with the topology fixed at 1 (the firmware's callback)
 RANGES["synth"] = RANGES["voice"] + RANGES["fxrack"][:-1] + [1.0]
+# the Svf synth: the same fields, each instrument's rack topology drawn from {0, 1}
+RANGES["synth_svf"] = RANGES["voice"] + RANGES["fxrack"][:-1] + ["int2"]
 
 
 def _splitmix64(z: np.ndarray) -> np.ndarray:
@@ -66,8 +68,8 @@ def instance_params(kind: str, first: int, count: int, seed: int = 0) -> np.ndar
     for f, r in enumerate(RANGES[kind]):
         if isinstance(r, float):
             rows.append(np.full(count, r, np.float32))
-        elif r == "int5":
-            rows.append(np.floor(uniform01(seed, f, first, count) * 5).astype(np.float32))
+        elif r in ("int5", "int2"):
+            rows.append(np.floor(uniform01(seed, f, first, count) * int(r[3:])).astype(np.float32))
         else:
             lo, hi = r
             rows.append((lo + (hi - lo) * uniform01(seed, f, first, count)).astype(np.float32))

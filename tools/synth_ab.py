@@ -7,7 +7,9 @@
             (fxrack_block_v3): three launches per block, every voice sample and every bus sample
             through HBM (8 voices + 8 B per instrument-frame).
 Both get the same per-instrument parameters (workload.RANGES["synth"]) and every voice a NoteOn before
-the first block.  Device events around `--steps` blocks per window; at least 50 warm-up launches of
+the first block.  --kind synth_svf times the Svf synth instead: synth_svf_block_v1 against
+voice_block_v5 (OLFX_KIND_VOICE) + voice_mix + fxrack_block_v3, with workload.RANGES["synth_svf"] and every
+instrument's rack at --topology (0 or 1; the composed rack engine gets the same).  Device events around `--steps` blocks per window; at least 50 warm-up launches of
 each path; `--reps` windows per path, the order of the two paths rotated from one repetition to the
 next, in one process.  Prints one JSON line (medians, min-max, the verdict by the rule below, and
 whether the two paths' last blocks -- the same block of the same stream -- agree bit for bit).
@@ -16,6 +18,7 @@ The verdict: "faster" only if the fused median lies below the composed median by
 larger of the two min-max spreads; "slower" by the same rule the other way; else "tie".
 
   python tools/synth_ab.py [--instances 16384] [--voices 4] [--block 256] [--steps 50] [--reps 7]
+  python tools/synth_ab.py --kind synth_svf --topology 0 [--voices 1|4|8]
   python tools/synth_ab.py --only fused --steps 10      # untimed, for a rocprofv3 --pmc run
 """
 import argparse
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--kind", choices=["synth", "synth_svf"], default="synth")
+    ap.add_argument("--topology", type=int, choices=[0, 1], default=1, help="synth_svf: every instrument's rack topology")
     ap.add_argument("--only", choices=["fused", "composed"], help="run one path untimed (profiler runs)")
     args = ap.parse_args()
 
@@ -48,21 +53,25 @@ def main():
         sys.exit("synth_ab: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
     n, P, B = args.instances, args.voices, args.block
-    p = workload.instance_params("synth", 0, n)
+    svf = args.kind == "synth_svf"
+    if args.topology != 1 and not svf:
+        sys.exit("synth_ab: the Moog synth runs topology 1 only")
+    p = workload.instance_params(args.kind, 0, n)
     nv = len(ofx.PARAMS[ofx.KIND_VOICE])
+    p[nv + ofx.PARAMS[ofx.KIND_FXRACK].index("topology")] = float(args.topology)
     notes = workload.voice_notes(0, n * P).reshape(n, P)
     out = torch.empty((2, B, n), device=dev)
     out_c = torch.empty((2, B, n), device=dev)
 
     paths = {}
     if args.only != "composed":
-        fused = ofx.Engine("synth", n, block=B, voices=P)
+        fused = ofx.Engine(args.kind, n, block=B, voices=P)
         fused.set_params(0, p)
         for q in range(P):                                   # voice q of every instrument
             fused.note_events(ofx.Engine.make_events(np.arange(n), 1, notes[:, q]))
         paths["fused"] = lambda k: fused.process(None, out=out)
     if args.only != "fused":
-        voice, rack = ofx.Engine("voice_moog", n * P, block=B), ofx.Engine("fxrack", n, block=B)
+        voice, rack = ofx.Engine("voice" if svf else "voice_moog", n * P, block=B), ofx.Engine("fxrack", n, block=B)
         # voice i * P + q is voice q of instrument i: contiguous buses, the mix's fastest path (float4 runs)
         voice.set_params(0, np.repeat(p[:nv], P, axis=1))
         rack.set_params(0, p[nv:])
@@ -91,14 +100,14 @@ def main():
         window(run, max(args.warmup, 50 if not args.only else 2))
     if args.only:
         window(paths[args.only], args.steps)
-        print(json.dumps({"only": args.only, "instances": n, "voices": P, "block": B, "steps": args.steps}))
+        print(json.dumps({"only": args.only, "kind": args.kind, "topology": args.topology, "instances": n, "voices": P, "block": B, "steps": args.steps}))
         return
     names = list(paths)
     us = {name: [] for name in names}
     for r in range(args.reps):
         for name in names[r % 2:] + names[:r % 2]:          # rotated
             us[name].append(window(paths[name], args.steps))
-    res = {"instances": n, "voices": P, "block": B, "steps": args.steps, "reps": args.reps, "warmup": max(args.warmup, 50),
+    res = {"kind": args.kind, "topology": args.topology, "instances": n, "voices": P, "block": B, "steps": args.steps, "reps": args.reps, "warmup": max(args.warmup, 50),
            "kernels": {"fused": fused.kernel_name, "composed": [voice.kernel_name, "voice_mix", rack.kernel_name]},
            "device": torch.cuda.get_device_name(0)}
     for name, v in us.items():
@@ -116,6 +125,9 @@ def main():
     torch.cuda.synchronize()
     res["last_block_bit_identical"] = bool(torch.equal(out.view(torch.int32), out_c.view(torch.int32)))
     res["last_block_nonzero_finite"] = bool(torch.isfinite(out).all() and (out != 0).any())
+    # (the Svf voice's drive term can run a voice of the workload's draw away to a non-finite level)
+    res["last_block_nonfinite_instruments"] = int((~torch.isfinite(out)).any(dim=0).any(dim=0).sum())
+    res["last_block_silent_instruments"] = int((out[0] == 0).all(dim=0).sum())
     print(json.dumps(res))
 
 
