@@ -226,37 +226,26 @@ size_t carve(olfx_engine *e, char *base) {
 // modules/juce/host/host.cpp:646-653): O(changed), asynchronous, no host<->device round trip.
 // ---------------------------------------------------------------------------------------------
 
-// The destination arrays (field-major, CoefScatterArgs) of a coefficient record's segments
-// (host::coef_segments); returns the record's words.
+// The destination arrays (field-major, CoefScatterArgs) of a coefficient record's segments: each part
+// of the kind goes to the array its row names (host::Dst); returns the record's words.
 uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
+    const struct { void *p; uint32_t stride; } to[host::TO_COUNT] = {
+        /* TO_DT */ {e->dt_coef, e->n_dt},       // padding plate instances keep their zeroed coefficients
+        /* TO_CH */ {e->ch_coef, e->n},
+        /* TO_PS */ {e->ps_coef, e->n},
+        /* TO_VC */ {e->vc_coef, e->n},
+        /* TO_FR */ {e->fr_coef, e->n},
+        /* TO_SM */ {e->sm_asg, e->n},
+    };
+    const host::KindDesc &kd = *e->hs.kd;
     const host::Segments sg = host::coef_segments(e->kind);
-    void *dst[3] = {nullptr, nullptr, nullptr};
-    uint32_t stride[3] = {e->n, e->n, e->n};
-    switch (e->kind) {
-    case OLFX_KIND_DATTORRO: dst[0] = e->dt_coef; stride[0] = e->n_dt; break;
-    case OLFX_KIND_CHORUS:
-    case OLFX_KIND_PITCHSHIFT: dst[0] = e->ch_coef; break;
-    case OLFX_KIND_CHAIN:       // padding reverb instances keep their zeroed coefficients
-        dst[0] = e->ch_coef; dst[1] = e->ps_coef; dst[2] = e->dt_coef; stride[2] = e->n_dt;
-        break;
-    case OLFX_KIND_FXRACK: dst[0] = e->fr_coef; break;
-    case OLFX_KIND_PLATERACK:   // padding plate instances keep their zeroed coefficients
-        dst[0] = e->fr_coef; dst[1] = e->dt_coef; stride[1] = e->n_dt;
-        break;
-    case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG: dst[0] = e->vc_coef; break;
-    case OLFX_KIND_VOICE_SAMPLE: dst[0] = e->vc_coef; dst[1] = e->sm_asg; break;
-    case OLFX_KIND_SYNTH:
-    case OLFX_KIND_SYNTH_SVF: dst[0] = e->vc_coef; dst[1] = e->fr_coef; break;
-    default: break;
-    }
     a->nseg = sg.nseg;
     for (uint32_t k = 0; k < sg.nseg; ++k) {
-        a->dst[k] = (uint32_t *)dst[k];
+        a->dst[k] = (uint32_t *)to[kd.parts[k].dst].p;
         a->words[k] = sg.words[k];
-        a->stride[k] = stride[k];
+        a->stride[k] = to[kd.parts[k].dst].stride;
     }
-    return sg.total();
+    return kd.words;
 }
 
 // Record one marker after the pending slots' kernels (on their stream) and make it their guard.
@@ -621,14 +610,8 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
     return OLFX_OK;
 }
 
-// Kinds whose kernels address the audio planes with 32-bit buffer offsets from `in` / `out`.
-bool planes_32bit(int kind) {
-    return kind == OLFX_KIND_CHORUS || kind == OLFX_KIND_PITCHSHIFT || kind == OLFX_KIND_CHAIN ||
-           kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK;
-}
-
-// All n_frames of a call, as frame tiles where a launch's planes would leave the kernels' 32-bit
-// offset range (planes_32bit): a tile is frames [f0, f0 + F) at in + f0 n with the caller's
+// All n_frames of a call, as frame tiles where a launch's planes would leave the kernel's 32-bit
+// offset range (KindDesc::planes_32bit): a tile is frames [f0, f0 + F) at in + f0 n with the caller's
 // plane distance, so the launch spans plane + F n floats (< 4 GiB); when the caller's planes alone
 // are >= 4 GiB apart, tiles are staged through a compact device buffer.  Frames run in order and
 // the state carries between launches, so tiles compute exactly what one launch would.  The note
@@ -637,7 +620,7 @@ int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, h
     const uint64_t n = e->n, plane = (uint64_t)n_frames * n;
     const uint64_t lim = (1ull << 30) - 1;                     // floats addressable in 32-bit bytes
     const VoiceArgs none{};
-    if (!planes_32bit(e->kind) || plane + plane <= lim) {
+    if (!e->hs.kd->planes_32bit || plane + plane <= lim) {
         const int rc = launch(e, in, out, n_frames, plane, s, ev);
         if (rc) return rc;
         e->frames += n_frames;
@@ -771,7 +754,7 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     if (const char *cb = std::getenv("OLFX_COPY_BYTES"))
         e->copy_bytes = std::min<size_t>((size_t)std::strtoull(cb, nullptr, 10), olfx_engine::kCopyBytes);
     host::chorus_sizes(sample_rate, &e->psize, &e->csize);
-    e->n_dt = kind == OLFX_KIND_CHAIN || kind == OLFX_KIND_PLATERACK ? (n_inst + 63u) & ~63u : n_inst;
+    e->n_dt = e->hs.kd->pad_plate ? (n_inst + 63u) & ~63u : n_inst;
 
     hipError_t r = hipSetDevice(device);
     if (r == hipSuccess) r = hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -1117,21 +1100,8 @@ double olfx_algorithmic_read_bytes_per_frame(const olfx_engine *e) {
 
 const char *olfx_kernel_name(const olfx_engine *e) {
     if (!e) return "";
-    switch (e->kind) {
-    case OLFX_KIND_DATTORRO:   // the network of the last block (dattorro.hip dattorro_network)
-        return dattorro_network_name(e->dt_net);
-    case OLFX_KIND_CHORUS:
-    case OLFX_KIND_PITCHSHIFT: return "chorus_block_v11";
-    case OLFX_KIND_VOICE: return "voice_block_v5";
-    case OLFX_KIND_VOICE_MOOG: return "voice_block_v4";
-    case OLFX_KIND_VOICE_SAMPLE: return "sampler_block_v1";
-    case OLFX_KIND_CHAIN: return "chain_block_v5";
-    case OLFX_KIND_FXRACK: return "fxrack_block_v3";
-    case OLFX_KIND_PLATERACK: return "platerack_block_v1";
-    case OLFX_KIND_SYNTH: return "synth_block_v1";
-    case OLFX_KIND_SYNTH_SVF: return "synth_svf_block_v1";
-    default: return "";
-    }
+    // the standalone reverb's: the network of the last block (dattorro.hip dattorro_network)
+    return e->hs.kd->kernel ? e->hs.kd->kernel : dattorro_network_name(e->dt_net);
 }
 
 const char *olfx_last_error(const olfx_engine *e) {

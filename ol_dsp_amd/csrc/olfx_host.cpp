@@ -22,10 +22,6 @@ uint32_t pow2_at_least(uint32_t x) {
 
 float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// the most parameters a kind has (an instance's parameters on the stack)
-constexpr uint32_t kMaxParams = std::max({(uint32_t)OLFX_CN_NPARAMS, (uint32_t)OLFX_VC_NPARAMS, (uint32_t)OLFX_PR_NPARAMS,
-                                          (uint32_t)OLFX_SY_NPARAMS});
-
 // a fraction of a cycle in [0, 1] as 64-bit fixed point (2^64 = one cycle); 1.0 wraps to 0
 uint64_t fix64(double cycles) {
     constexpr double kTwo64 = 18446744073709551616.0;
@@ -43,29 +39,6 @@ size_t up4(size_t x) { return (x + 3) & ~(size_t)3; }
 
 }  // namespace
 
-// ---------------------------------------------------------------------------------------------
-// Per-kind constants
-// ---------------------------------------------------------------------------------------------
-uint32_t n_params_of(int kind) {
-    switch (kind) {
-    case OLFX_KIND_DATTORRO: return OLFX_DT_NPARAMS;
-    case OLFX_KIND_CHORUS: return OLFX_CH_NPARAMS;
-    case OLFX_KIND_PITCHSHIFT: return OLFX_PS_NPARAMS;
-    case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG:
-    case OLFX_KIND_VOICE_SAMPLE: return OLFX_VC_NPARAMS;
-    case OLFX_KIND_CHAIN: return OLFX_CN_NPARAMS;
-    case OLFX_KIND_FXRACK: return OLFX_FR_NPARAMS;
-    case OLFX_KIND_PLATERACK: return OLFX_PR_NPARAMS;
-    case OLFX_KIND_SYNTH:
-    case OLFX_KIND_SYNTH_SVF: return OLFX_SY_NPARAMS;
-    default: return 0;
-    }
-}
-
-uint32_t in_channels(int kind) { return is_voice_kind(kind) || is_synth_kind(kind) ? 0u : 2u; }
-uint32_t out_channels(int kind) { return is_voice_kind(kind) ? 1u : 2u; }
-
 // ol::core::scale (modules/corelib/ol_corelib.h:27-44), t_sample = float
 float core_scale(float in, float inlow, float inhigh, float outlow, float outhigh, float power) {
     const float denom = inhigh - inlow;
@@ -77,172 +50,80 @@ float core_scale(float in, float inlow, float inhigh, float outlow, float outhig
     return (value * outdiff) + outlow;
 }
 
-void default_params(int kind, float *p) {
-    switch (kind) {
-    case OLFX_KIND_DATTORRO:
-        // verb.cpp:215-221
-        p[OLFX_DT_PREDELAY] = (float)0.1;
-        p[OLFX_DT_PREFILTER] = (float)0.85;
-        p[OLFX_DT_INPUT_DIFFUSION1] = (float)0.75;
-        p[OLFX_DT_INPUT_DIFFUSION2] = (float)0.625;
-        p[OLFX_DT_DECAY_DIFFUSION] = (float)0.70;
-        p[OLFX_DT_DECAY] = (float)0.75;
-        p[OLFX_DT_DAMPING] = (float)0.95;
-        break;
-    case OLFX_KIND_CHORUS:
-        // mono-chorus.rnbopat param boxes (:431,1772,2226,2660,3420,3854,4353)
-        p[OLFX_CH_PITCH] = 0.0f;
-        p[OLFX_CH_MIX] = 0.5f;
-        p[OLFX_CH_Q] = 0.5f;
-        p[OLFX_CH_CUTOFF] = 0.3f;
-        p[OLFX_CH_PHASE] = 1.0f;
-        p[OLFX_CH_DEPTH] = 0.5f;
-        p[OLFX_CH_RATE] = 0.2f;
-        p[OLFX_CH_WINDOW] = 10.0f;
-        break;
-    case OLFX_KIND_PITCHSHIFT:
-        p[OLFX_PS_SHIFT] = 0.0f;
-        p[OLFX_PS_WINDOW] = 10.0f;
-        break;
-    case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG:
-    case OLFX_KIND_VOICE_SAMPLE:
-        // SynthVoice member defaults (SynthVoice.h:285-311); Config order (Voice.h:14-31)
-        p[OLFX_VC_FILTER_CUTOFF] = 0.0f;
-        p[OLFX_VC_FILTER_RESONANCE] = 0.0f;
-        p[OLFX_VC_FILTER_DRIVE] = 0.0f;
-        p[OLFX_VC_FILTER_ENV_AMOUNT] = 1.0f;
-        p[OLFX_VC_FILTER_ATTACK] = 0.0f;
-        p[OLFX_VC_FILTER_ATTACK_SHAPE] = 1.0f;
-        p[OLFX_VC_FILTER_DECAY] = 0.2f;
-        p[OLFX_VC_FILTER_SUSTAIN] = 0.0f;
-        p[OLFX_VC_FILTER_RELEASE] = 0.0f;
-        p[OLFX_VC_AMP_ENV_AMOUNT] = 0.8f;
-        p[OLFX_VC_AMP_ATTACK] = 0.01f;
-        p[OLFX_VC_AMP_ATTACK_SHAPE] = 1.0f;
-        p[OLFX_VC_AMP_DECAY] = 0.0f;
-        p[OLFX_VC_AMP_SUSTAIN] = 1.0f;
-        p[OLFX_VC_AMP_RELEASE] = 0.01f;
-        p[OLFX_VC_PORTAMENTO] = 0.0f;
-        break;
-    case OLFX_KIND_CHAIN:
-        default_params(OLFX_KIND_CHORUS, p + OLFX_CN_CHORUS0);
-        default_params(OLFX_KIND_PITCHSHIFT, p + OLFX_CN_PITCH0);
-        default_params(OLFX_KIND_DATTORRO, p + OLFX_CN_VERB0);
-        break;
-    case OLFX_KIND_FXRACK:
-        // Fx.h member defaults; DelayFx::Init sets its filter through UpdateMidiControl(CC, 64 / 24)
-        p[OLFX_FR_DELAY_TIME] = 0.5f;
-        p[OLFX_FR_DELAY_FEEDBACK] = 0.5f;
-        p[OLFX_FR_DELAY_BALANCE] = 0.33f;
-        p[OLFX_FR_DELAY_CUTOFF] = core_scale(64.f, 0.f, 127.f, 0.f, 20000.f, 1.f);
-        p[OLFX_FR_DELAY_RESONANCE] = core_scale(24.f, 0.f, 127.f, 0.f, 1.f, 1.f);
-        p[OLFX_FR_REVERB_BALANCE] = 0.1f;
-        p[OLFX_FR_FILTER_CUTOFF] = 20000.f;
-        p[OLFX_FR_FILTER_RESONANCE] = 0.f;
-        p[OLFX_FR_FILTER_DRIVE] = 0.f;
-        p[OLFX_FR_FILTER_TYPE] = 0.f;
-        p[OLFX_FR_MASTER_VOLUME] = 0.8f;
-        p[OLFX_FR_TOPOLOGY] = 0.f;
-        break;
-    case OLFX_KIND_PLATERACK:
-        default_params(OLFX_KIND_FXRACK, p + OLFX_PR_RACK0);
-        // the plate as ReverbFx::Init -> Update() would set it through the glue of ReverbFx.cpp:29-37
-        // (members Fx.h:274-281) where the member lies in the setter's domain; `cutoff` (12000 Hz, for
-        // ReverbSc) does not and setPreDelay is never called: verb.cpp:215-221 for those two
-        default_params(OLFX_KIND_DATTORRO, p + OLFX_PR_VERB0);
-        p[OLFX_PR_VERB0 + OLFX_DT_PREFILTER] = 0.5f;          // pre_cutoff
-        p[OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION1] = 0.5f;   // input_diffusion1
-        p[OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION2] = 0.5f;   // input_diffusion2
-        p[OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION] = 0.5f;    // decay_diffusion
-        p[OLFX_PR_VERB0 + OLFX_DT_DECAY] = 0.5f;              // decay_time
-        break;
-    case OLFX_KIND_SYNTH:
-        // the firmware's objects (main.cpp:49-67): SynthVoice members, then delay_fx / reverb_fx /
-        // filter_fx as the rack's members, in the callback's topology
-        default_params(OLFX_KIND_VOICE_MOOG, p + OLFX_SY_VOICE0);
-        default_params(OLFX_KIND_FXRACK, p + OLFX_SY_RACK0);
-        p[OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY] = 1.f;
-        break;
-    case OLFX_KIND_SYNTH_SVF:
-        // the library's default-constructed SynthVoice behind the same rack, the firmware's callback first
-        default_params(OLFX_KIND_VOICE, p + OLFX_SY_VOICE0);
-        default_params(OLFX_KIND_FXRACK, p + OLFX_SY_RACK0);
-        p[OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY] = 1.f;
-        break;
-    default: break;
-    }
+// ---- the components' defaults (the reference's, of the user-facing parameters) ----
+namespace {
+
+void plate_defaults(float *p) {
+    // verb.cpp:215-221
+    p[OLFX_DT_PREDELAY] = (float)0.1;
+    p[OLFX_DT_PREFILTER] = (float)0.85;
+    p[OLFX_DT_INPUT_DIFFUSION1] = (float)0.75;
+    p[OLFX_DT_INPUT_DIFFUSION2] = (float)0.625;
+    p[OLFX_DT_DECAY_DIFFUSION] = (float)0.70;
+    p[OLFX_DT_DECAY] = (float)0.75;
+    p[OLFX_DT_DAMPING] = (float)0.95;
 }
+
+void chorus_defaults(float *p) {
+    // mono-chorus.rnbopat param boxes (:431,1772,2226,2660,3420,3854,4353)
+    p[OLFX_CH_PITCH] = 0.0f;
+    p[OLFX_CH_MIX] = 0.5f;
+    p[OLFX_CH_Q] = 0.5f;
+    p[OLFX_CH_CUTOFF] = 0.3f;
+    p[OLFX_CH_PHASE] = 1.0f;
+    p[OLFX_CH_DEPTH] = 0.5f;
+    p[OLFX_CH_RATE] = 0.2f;
+    p[OLFX_CH_WINDOW] = 10.0f;
+}
+
+void pitch_defaults(float *p) {
+    p[OLFX_PS_SHIFT] = 0.0f;
+    p[OLFX_PS_WINDOW] = 10.0f;
+}
+
+void voice_defaults(float *p) {
+    // SynthVoice member defaults (SynthVoice.h:285-311); Config order (Voice.h:14-31)
+    p[OLFX_VC_FILTER_CUTOFF] = 0.0f;
+    p[OLFX_VC_FILTER_RESONANCE] = 0.0f;
+    p[OLFX_VC_FILTER_DRIVE] = 0.0f;
+    p[OLFX_VC_FILTER_ENV_AMOUNT] = 1.0f;
+    p[OLFX_VC_FILTER_ATTACK] = 0.0f;
+    p[OLFX_VC_FILTER_ATTACK_SHAPE] = 1.0f;
+    p[OLFX_VC_FILTER_DECAY] = 0.2f;
+    p[OLFX_VC_FILTER_SUSTAIN] = 0.0f;
+    p[OLFX_VC_FILTER_RELEASE] = 0.0f;
+    p[OLFX_VC_AMP_ENV_AMOUNT] = 0.8f;
+    p[OLFX_VC_AMP_ATTACK] = 0.01f;
+    p[OLFX_VC_AMP_ATTACK_SHAPE] = 1.0f;
+    p[OLFX_VC_AMP_DECAY] = 0.0f;
+    p[OLFX_VC_AMP_SUSTAIN] = 1.0f;
+    p[OLFX_VC_AMP_RELEASE] = 0.01f;
+    p[OLFX_VC_PORTAMENTO] = 0.0f;
+}
+
+void rack_defaults(float *p) {
+    // Fx.h member defaults; DelayFx::Init sets its filter through UpdateMidiControl(CC, 64 / 24)
+    p[OLFX_FR_DELAY_TIME] = 0.5f;
+    p[OLFX_FR_DELAY_FEEDBACK] = 0.5f;
+    p[OLFX_FR_DELAY_BALANCE] = 0.33f;
+    p[OLFX_FR_DELAY_CUTOFF] = core_scale(64.f, 0.f, 127.f, 0.f, 20000.f, 1.f);
+    p[OLFX_FR_DELAY_RESONANCE] = core_scale(24.f, 0.f, 127.f, 0.f, 1.f, 1.f);
+    p[OLFX_FR_REVERB_BALANCE] = 0.1f;
+    p[OLFX_FR_FILTER_CUTOFF] = 20000.f;
+    p[OLFX_FR_FILTER_RESONANCE] = 0.f;
+    p[OLFX_FR_FILTER_DRIVE] = 0.f;
+    p[OLFX_FR_FILTER_TYPE] = 0.f;
+    p[OLFX_FR_MASTER_VOLUME] = 0.8f;
+    p[OLFX_FR_TOPOLOGY] = 0.f;
+}
+
+}  // namespace
 
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize) {
     // pitch ring: delays up to W = 10 ms plus the interpolation neighbour
     *psize = pow2_at_least((uint32_t)std::ceil(10.0 * sr / 1000.0) + 2);
     // chorus ring: delays up to 2 D, D <= 12 ms (delay~ @maxsize samplerate*2 is never reached)
     *csize = pow2_at_least(2u * (uint32_t)std::ceil(12.0 * sr / 1000.0) + 2);
-}
-
-uint64_t state_bytes(int kind, uint32_t n, float sr) {
-    uint32_t ps, cs;
-    chorus_sizes(sr, &ps, &cs);
-    const uint64_t dt = (uint64_t)dt_total_floats() * 4 + DTS_N * 4 + DTC_N * 4;
-    const uint64_t ch = (uint64_t)2 * (ps + cs) * 4 + CHS_N * 4 + CHC_N * 4;
-    const uint64_t vc = (uint64_t)VCS_N * 4 + VCC_N * 4;
-    switch (kind) {
-    case OLFX_KIND_DATTORRO: return dt * n;
-    case OLFX_KIND_CHORUS:
-    case OLFX_KIND_PITCHSHIFT: return ch * n;
-    case OLFX_KIND_VOICE: return vc * n;
-    case OLFX_KIND_VOICE_MOOG: return vc * n + (uint64_t)(VCS_N_MOOG - VCS_N) * 4 * n;
-    case OLFX_KIND_VOICE_SAMPLE: return (vc + (uint64_t)SMC_N * 4) * n;   // the bank is the caller's data, not state
-    case OLFX_KIND_CHAIN: return (dt + 2 * ch) * n;
-    case OLFX_KIND_FXRACK: return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n;
-    case OLFX_KIND_PLATERACK:       // the rack's ring + the plate's, the plate's instances padded to 64
-        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n + dt * ((n + 63u) & ~63u);
-    case OLFX_KIND_SYNTH:           // the rack's, one set of voice coefficients, four voices' state
-        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4 + VCC_N * 4 +
-                (uint64_t)kSynthDefaultVoices * VCS_N_MOOG * 4) * n;
-    case OLFX_KIND_SYNTH_SVF:       // the same with OLFX_KIND_VOICE's per-voice state
-        return ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4 + VCC_N * 4 +
-                (uint64_t)kSynthDefaultVoices * VCS_N * 4) * n;
-    default: return 0;
-    }
-}
-
-double algorithmic_bytes_per_frame(int kind) {
-    // DESIGN.md section 4 / SURVEY.md section 8d, B = 256: compulsory ring traffic + I/O
-    switch (kind) {
-    case OLFX_KIND_DATTORRO: return 164.6;     // 148.6 state + 8 in + 8 out (stereo in)
-    case OLFX_KIND_CHORUS: return 56.0;        // 2 x (pitch w + 2 taps + chorus w + tap) x 4 + 16 I/O
-    case OLFX_KIND_PITCHSHIFT: return 40.0;    // 2 x (w + 2 taps) x 4 + 16 I/O
-    case OLFX_KIND_VOICE: return 5.4;          // 4 B out + per-block state
-    case OLFX_KIND_VOICE_MOOG: return 5.7;     // 4 B out + per-block state (9 more state words)
-    case OLFX_KIND_VOICE_SAMPLE: return 8.0;   // 4 B of the sample read + 4 B out
-    case OLFX_KIND_CHAIN: return 228.6;
-    case OLFX_KIND_FXRACK: return 32.0;       // ring write 8 + ring read 8 + I/O 16 per stereo frame
-    case OLFX_KIND_PLATERACK: return 32.0 + 164.6 - 16.0;   // rack + plate - the plate's own I/O (in LDS now)
-    case OLFX_KIND_SYNTH:                      // the rack at topology 1 with no input read: ring 8 + 8, out 8
-    case OLFX_KIND_SYNTH_SVF: return 32.0 - 8.0;   // (topology 0 stores its zero channel too: the same)
-    default: return 0.0;
-    }
-}
-
-double algorithmic_read_bytes_per_frame(int kind) {
-    // the read share of the figures above (the north star's "HBM-read roofline"): every tap read
-    // of data older than the block, counted once, plus the input
-    switch (kind) {
-    case OLFX_KIND_DATTORRO: return 6445.0 * 4.0 / 256.0 + 8.0;   // 27 taps: sum min(d, 256) = 6,445 floats; + 8 in
-    case OLFX_KIND_CHORUS: return 32.0;        // 2 x (2 pitch taps + chorus tap) x 4 + 8 in
-    case OLFX_KIND_PITCHSHIFT: return 24.0;    // 2 x 2 taps x 4 + 8 in
-    case OLFX_KIND_VOICE: return 0.7;          // per-block state and coefficients
-    case OLFX_KIND_VOICE_MOOG: return 0.85;
-    case OLFX_KIND_VOICE_SAMPLE: return 4.0;   // the sample
-    case OLFX_KIND_CHAIN: return 8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0;   // 148.7
-    case OLFX_KIND_FXRACK: return 16.0;        // ring read 8 + in 8
-    case OLFX_KIND_PLATERACK: return 16.0 + 6445.0 * 4.0 / 256.0;   // rack + the plate's taps (its input is in LDS)
-    case OLFX_KIND_SYNTH:
-    case OLFX_KIND_SYNTH_SVF: return 16.0 - 8.0;   // the ring read; the input never leaves LDS
-    default: return 0.0;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -256,17 +137,18 @@ uint32_t dattorro_predelay_samples(float v) {
     return d <= 0.0f ? 0u : ((uint32_t)(uint16_t)d & (kDtSize[DT_PRE] - 1u));
 }
 
-void derive_dattorro(const float *p, float *c) {
-    c[DTC_PREFILTER] = p[OLFX_DT_PREFILTER];
-    c[DTC_IN1] = p[OLFX_DT_INPUT_DIFFUSION1];
-    c[DTC_IN2] = p[OLFX_DT_INPUT_DIFFUSION2];
-    c[DTC_DD1] = p[OLFX_DT_DECAY_DIFFUSION];
-    c[DTC_DAMPING] = p[OLFX_DT_DAMPING];
-    c[DTC_DECAY] = p[OLFX_DT_DECAY];
+// plate: p = [OLFX_DT_*], c = [DTC_*] (floats, as u32 words)
+void derive_dattorro(const float *p, uint32_t *c) {
+    c[DTC_PREFILTER] = as_u32(p[OLFX_DT_PREFILTER]);
+    c[DTC_IN1] = as_u32(p[OLFX_DT_INPUT_DIFFUSION1]);
+    c[DTC_IN2] = as_u32(p[OLFX_DT_INPUT_DIFFUSION2]);
+    c[DTC_DD1] = as_u32(p[OLFX_DT_DECAY_DIFFUSION]);
+    c[DTC_DAMPING] = as_u32(p[OLFX_DT_DAMPING]);
+    c[DTC_DECAY] = as_u32(p[OLFX_DT_DECAY]);
     // verb.cpp:49,162-165: clamp(t_sample x, ...) narrows value+0.15 to float
     float x = (float)((double)p[OLFX_DT_DECAY] + 0.15);
-    c[DTC_DD2] = x < 0.25f ? 0.25f : (x > 0.5f ? 0.5f : x);
-    c[DTC_PREDELAY] = (float)dattorro_predelay_samples(p[OLFX_DT_PREDELAY]);
+    c[DTC_DD2] = as_u32(x < 0.25f ? 0.25f : (x > 0.5f ? 0.5f : x));
+    c[DTC_PREDELAY] = as_u32((float)dattorro_predelay_samples(p[OLFX_DT_PREDELAY]));
 }
 
 // chorus: p = [OLFX_CH_*], c = [CHC_*] (u32 words)
@@ -320,7 +202,7 @@ void derive_chorus(const float *p, double sr, uint32_t *c) {
 // pitch-shift stage only: reuse the chorus coefficient block (mode 1 ignores the rest)
 void derive_pitchshift(const float *p, double sr, uint32_t *c) {
     float cp[OLFX_CH_NPARAMS];
-    default_params(OLFX_KIND_CHORUS, cp);
+    chorus_defaults(cp);
     cp[OLFX_CH_PITCH] = p[OLFX_PS_SHIFT];
     cp[OLFX_CH_WINDOW] = p[OLFX_PS_WINDOW];
     derive_chorus(cp, sr, c);
@@ -383,8 +265,8 @@ void derive_fxrack(const float *p, float sr, uint32_t *c) {
 
 // Voice: `configured` = false reproduces SynthVoice::Init without any Update()
 // (SynthVoice.h:31-39): DaisySP Init defaults in the envelopes and the Svf.
-void derive_voice(const float *p, bool configured, bool moog, float sr, float *c) {
-    float tgt;
+void derive_voice(const float *p, bool configured, bool moog, float sr, uint32_t *w) {
+    float c[VCC_N], tgt;
     if (!configured) {
         // daisysp::Adsr::Init: attack 0.1 s shape 0, decay 0.1 s, release 0.1 s, sustain 0.7
         c[VCC_ATK_D0A] = adsr_attack_d0(0.1f, 0.0f, sr, &tgt); c[VCC_ATK_TGT_A] = tgt;
@@ -434,63 +316,202 @@ void derive_voice(const float *p, bool configured, bool moog, float sr, float *c
         c[VCC_LADDER_DRIVE] = 0.5f;
         c[VCC_LADDER_WREC] = 1.0f / (sr * 4);
     }
+    std::memcpy(w, c, sizeof c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The components and the kind table: each kind is stated once, here.  The per-kind functions below, the
+// shadow (through the row it looks up in init) and olfx_engine.cpp (scatter destinations, plane
+// addressing, plate padding, kernel name) read the row.  Adding a kind that composes existing components
+// takes one row here and a `launch` case in olfx_engine.cpp.  It takes a line in `carve` where no kind
+// has that set of device arrays yet.  Its field names go into include/olfx.h and engine.py's PARAMS.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct Component {
+    uint32_t n_params, words;                    // user-facing parameters, coefficient words
+    void (*defaults)(float *p);                  // the reference's defaults; null: no parameters
+    // instance i's coefficient words from the component's parameters p
+    void (*derive)(const float *p, const Shadow &s, uint32_t i, uint32_t *w);
+};
+constexpr Component kComponents[CP_COUNT] = {
+    /* CP_PLATE  */ {OLFX_DT_NPARAMS, DTC_N, plate_defaults,
+                     [](const float *p, const Shadow &, uint32_t, uint32_t *w) { derive_dattorro(p, w); }},
+    /* CP_CHORUS */ {OLFX_CH_NPARAMS, CHC_N, chorus_defaults,
+                     [](const float *p, const Shadow &s, uint32_t, uint32_t *w) { derive_chorus(p, s.sr, w); }},
+    /* CP_PITCH  */ {OLFX_PS_NPARAMS, CHC_N, pitch_defaults,
+                     [](const float *p, const Shadow &s, uint32_t, uint32_t *w) { derive_pitchshift(p, s.sr, w); }},
+    /* CP_VOICE  */ {OLFX_VC_NPARAMS, VCC_N, voice_defaults,
+                     [](const float *p, const Shadow &s, uint32_t i, uint32_t *w) {
+                         derive_voice(p, s.configured[i] != 0, s.kd->moog, s.sr, w);
+                     }},
+    /* CP_RACK   */ {OLFX_FR_NPARAMS, FRC_N, rack_defaults,
+                     [](const float *p, const Shadow &s, uint32_t, uint32_t *w) { derive_fxrack(p, s.sr, w); }},
+    // the voice's Sample assignment: no parameters, its words come from olfx_sample_voices
+    /* CP_SAMPLE */ {0, SMC_N, nullptr,
+                     [](const float *, const Shadow &s, uint32_t i, uint32_t *w) { s.sample_record(i, w); }},
+};
+
+constexpr size_t kKinds = OLFX_KIND_SYNTH_SVF + 1;     // kind numbers 0 .. the last; 0 and 9 are no kinds
+
+constexpr std::array<KindDesc, kKinds> kKindTable = [] {
+    std::array<KindDesc, kKinds> t{};
+    auto row = [&t](int kind, std::initializer_list<Part> parts, const char *kernel, double bytes, double read_bytes)
+        -> KindDesc & {
+        KindDesc &k = t[(size_t)kind];
+        for (const Part &p : parts) {
+            k.parts[k.nparts++] = p;
+            k.n_params += kComponents[p.comp].n_params;
+            k.words += kComponents[p.comp].words;
+            if (p.comp == CP_PLATE) k.pre_field = p.field0 + OLFX_DT_PREDELAY;
+            if (p.comp == CP_RACK) k.topo_field = p.field0 + OLFX_FR_TOPOLOGY;
+            if (p.comp == CP_VOICE) k.voice0 = p.field0, k.voice_end = p.field0 + OLFX_VC_NPARAMS;
+            if (p.comp == CP_SAMPLE) k.has_sample = true;
+        }
+        k.kernel = kernel;
+        k.bytes_per_frame = bytes;
+        k.read_bytes_per_frame = read_bytes;
+        return k;
+    };
+    // The two figures of a row: DESIGN.md section 4 / SURVEY.md section 8d, B = 256: compulsory ring
+    // traffic + I/O; then its read share (the north star's "HBM-read roofline"): every tap read of data
+    // older than the block, counted once, plus the input.
+    KindDesc *k = nullptr;
+    // no fixed kernel: the network of the last block (dattorro.hip dattorro_network)
+    row(OLFX_KIND_DATTORRO, {{CP_PLATE, 0, TO_DT}}, nullptr,
+        164.6,                            // 148.6 state + 8 in + 8 out (stereo in)
+        6445.0 * 4.0 / 256.0 + 8.0);      // 27 taps: sum min(d, 256) = 6,445 floats; + 8 in
+    k = &row(OLFX_KIND_CHORUS, {{CP_CHORUS, 0, TO_CH}}, "chorus_block_v11",
+             56.0,                        // 2 x (pitch w + 2 taps + chorus w + tap) x 4 + 16 I/O
+             32.0);                       // 2 x (2 pitch taps + chorus tap) x 4 + 8 in
+    k->planes_32bit = true;
+    // alone, the pitch-shifter runs the chorus kernel over the chorus arrays
+    k = &row(OLFX_KIND_PITCHSHIFT, {{CP_PITCH, 0, TO_CH}}, "chorus_block_v11",
+             40.0,                        // 2 x (w + 2 taps) x 4 + 16 I/O
+             24.0);                       // 2 x 2 taps x 4 + 8 in
+    k->planes_32bit = true;
+    k = &row(OLFX_KIND_VOICE, {{CP_VOICE, 0, TO_VC}}, "voice_block_v5",
+             5.4,                         // 4 B out + per-block state
+             0.7);                        // per-block state and coefficients
+    k->in_ch = 0; k->out_ch = 1; k->instances = KindDesc::VOICES;
+    k = &row(OLFX_KIND_VOICE_MOOG, {{CP_VOICE, 0, TO_VC}}, "voice_block_v4",
+             5.7,                         // 4 B out + per-block state (9 more state words)
+             0.85);
+    k->in_ch = 0; k->out_ch = 1; k->instances = KindDesc::VOICES; k->moog = true;
+    // the voice, its Sample (the bank is the caller's data, not state)
+    k = &row(OLFX_KIND_VOICE_SAMPLE, {{CP_VOICE, 0, TO_VC}, {CP_SAMPLE, OLFX_VC_NPARAMS, TO_SM}}, "sampler_block_v1",
+             8.0,                         // 4 B of the sample read + 4 B out
+             4.0);                        // the sample
+    k->in_ch = 0; k->out_ch = 1; k->instances = KindDesc::VOICES;
+    // chorus, pitch-shift, reverb; in the chain the pitch-shifter has arrays of its own
+    k = &row(OLFX_KIND_CHAIN,
+             {{CP_CHORUS, OLFX_CN_CHORUS0, TO_CH}, {CP_PITCH, OLFX_CN_PITCH0, TO_PS}, {CP_PLATE, OLFX_CN_VERB0, TO_DT}},
+             "chain_block_v5", 228.6,
+             8.0 + 24.0 + 16.0 + 6445.0 * 4.0 / 256.0);   // 148.7
+    k->planes_32bit = true; k->pad_plate = true;
+    k = &row(OLFX_KIND_FXRACK, {{CP_RACK, 0, TO_FR}}, "fxrack_block_v3",
+             32.0,                        // ring write 8 + ring read 8 + I/O 16 per stereo frame
+             16.0);                       // ring read 8 + in 8
+    k->planes_32bit = true; k->topologies = 0x1F; k->topology_msg = "rack topology must be 0, 1, 2, 3 or 4";
+    // rack, plate
+    k = &row(OLFX_KIND_PLATERACK, {{CP_RACK, OLFX_PR_RACK0, TO_FR}, {CP_PLATE, OLFX_PR_VERB0, TO_DT}}, "platerack_block_v1",
+             32.0 + 164.6 - 16.0,                // rack + plate - the plate's own I/O (in LDS now)
+             16.0 + 6445.0 * 4.0 / 256.0);       // rack + the plate's taps (its input is in LDS)
+    k->planes_32bit = true; k->pad_plate = true; k->state_counts_padding = true;
+    // the plate as ReverbFx::Init -> Update() would set it through the glue of ReverbFx.cpp:29-37
+    // (members Fx.h:274-281) where the member lies in the setter's domain; `cutoff` (12000 Hz, for
+    // ReverbSc) does not and setPreDelay is never called: verb.cpp:215-221 for those two
+    k->set[k->nset++] = {OLFX_PR_VERB0 + OLFX_DT_PREFILTER, 0.5f};          // pre_cutoff
+    k->set[k->nset++] = {OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION1, 0.5f};   // input_diffusion1
+    k->set[k->nset++] = {OLFX_PR_VERB0 + OLFX_DT_INPUT_DIFFUSION2, 0.5f};   // input_diffusion2
+    k->set[k->nset++] = {OLFX_PR_VERB0 + OLFX_DT_DECAY_DIFFUSION, 0.5f};    // decay_diffusion
+    k->set[k->nset++] = {OLFX_PR_VERB0 + OLFX_DT_DECAY, 0.5f};              // decay_time
+    // the components alone (2..4) are the firmware's objects around the ReverbSc stub: no plate in them
+    k->topologies = 0x3; k->topology_msg = "plate rack topology must be 0 or 1";
+    // the firmware's objects (main.cpp:49-67): SynthVoice members, then delay_fx / reverb_fx /
+    // filter_fx as the rack's members, in the callback's topology
+    k = &row(OLFX_KIND_SYNTH, {{CP_VOICE, OLFX_SY_VOICE0, TO_VC}, {CP_RACK, OLFX_SY_RACK0, TO_FR}}, "synth_block_v1",
+             32.0 - 8.0,                  // the rack at topology 1 with no input read: ring 8 + 8, out 8
+             16.0 - 8.0);                 // the ring read; the input never leaves LDS
+    k->in_ch = 0; k->instances = KindDesc::INSTRUMENTS; k->moog = true;
+    k->set[k->nset++] = {OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY, 1.f};
+    // the firmware's callback is the only chain the synth kernel runs
+    k->topologies = 0x2; k->topology_msg = "synth rack topology must be 1";
+    // the library's default-constructed SynthVoice behind the same rack, the firmware's callback first
+    k = &row(OLFX_KIND_SYNTH_SVF, {{CP_VOICE, OLFX_SY_VOICE0, TO_VC}, {CP_RACK, OLFX_SY_RACK0, TO_FR}}, "synth_svf_block_v1",
+             32.0 - 8.0,                  // as the synth (topology 0 stores its zero channel too: the same)
+             16.0 - 8.0);
+    k->in_ch = 0; k->instances = KindDesc::INSTRUMENTS;
+    k->set[k->nset++] = {OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY, 1.f};
+    // the Svf synth runs the rack proper (0) as well; the components alone (2..4) have no voices in front
+    k->topologies = 0x3; k->topology_msg = "svf synth rack topology must be 0 or 1";
+    return t;
+}();
+
+// the most parameters a kind has (an instance's parameters on the stack)
+constexpr uint32_t kMaxParams = [] {
+    uint32_t m = 0;
+    for (const KindDesc &k : kKindTable) m = std::max(m, k.n_params);
+    return m;
+}();
+
+}  // namespace
+
+const KindDesc &kind_desc(int kind) { return kKindTable[(size_t)kind < kKinds ? (size_t)kind : 0]; }
+
+uint32_t n_params_of(int kind) { return kind_desc(kind).n_params; }
+uint32_t in_channels(int kind) { return kind_desc(kind).in_ch; }
+uint32_t out_channels(int kind) { return kind_desc(kind).out_ch; }
+bool takes_note_events(int kind) { return kind_desc(kind).takes_note_events(); }
+double algorithmic_bytes_per_frame(int kind) { return kind_desc(kind).bytes_per_frame; }
+double algorithmic_read_bytes_per_frame(int kind) { return kind_desc(kind).read_bytes_per_frame; }
+
+void default_params(int kind, float *p) {
+    const KindDesc &k = kind_desc(kind);
+    for (uint32_t j = 0; j < k.nparts; ++j)
+        if (const auto defaults = kComponents[k.parts[j].comp].defaults) defaults(p + k.parts[j].field0);
+    for (uint32_t j = 0; j < k.nset; ++j) p[k.set[j].field] = k.set[j].value;
 }
 
 Segments coef_segments(int kind) {
-    switch (kind) {
-    case OLFX_KIND_DATTORRO: return {1, {DTC_N, 0, 0}};
-    case OLFX_KIND_CHORUS:
-    case OLFX_KIND_PITCHSHIFT: return {1, {CHC_N, 0, 0}};
-    case OLFX_KIND_CHAIN: return {3, {CHC_N, CHC_N, DTC_N}};       // chorus, pitch-shift, reverb
-    case OLFX_KIND_FXRACK: return {1, {FRC_N, 0, 0}};
-    case OLFX_KIND_PLATERACK: return {2, {FRC_N, DTC_N, 0}};       // rack, plate
-    case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG: return {1, {VCC_N, 0, 0}};
-    case OLFX_KIND_VOICE_SAMPLE: return {2, {VCC_N, SMC_N, 0}};   // the voice, its Sample
-    case OLFX_KIND_SYNTH:
-    case OLFX_KIND_SYNTH_SVF: return {2, {VCC_N, FRC_N, 0}};      // the instrument's voices, its rack
-    default: return {0, {0, 0, 0}};
-    }
+    const KindDesc &k = kind_desc(kind);
+    Segments sg{k.nparts, {0, 0, 0}};
+    for (uint32_t j = 0; j < k.nparts; ++j) sg.words[j] = kComponents[k.parts[j].comp].words;
+    return sg;
+}
+
+// The figure olfx_kind_info_get publishes: every part's rings, state and coefficient words.  Not what the
+// engine allocates: the chain's second stage is counted with a chorus ring it does not have, and its plate
+// without the padding to 64 instances.
+uint64_t state_bytes(int kind, uint32_t n, float sr) {
+    const KindDesc &k = kind_desc(kind);
+    uint32_t ps, cs;
+    chorus_sizes(sr, &ps, &cs);
+    const uint64_t voices = k.instances == KindDesc::INSTRUMENTS ? kSynthDefaultVoices : 1u;
+    uint64_t bytes = 0;
+    for (uint32_t j = 0; j < k.nparts; ++j)
+        switch (k.parts[j].comp) {
+        case CP_PLATE:
+            bytes += ((uint64_t)dt_total_floats() * 4 + DTS_N * 4 + DTC_N * 4) * (k.state_counts_padding ? (n + 63u) & ~63u : n);
+            break;
+        case CP_CHORUS:
+        case CP_PITCH: bytes += ((uint64_t)2 * (ps + cs) * 4 + CHS_N * 4 + CHC_N * 4) * n; break;
+        // one set of voice coefficients, every voice's state
+        case CP_VOICE: bytes += ((uint64_t)VCC_N * 4 + voices * (k.moog ? VCS_N_MOOG : VCS_N) * 4) * n; break;
+        case CP_RACK: bytes += ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n; break;
+        case CP_SAMPLE: bytes += (uint64_t)SMC_N * 4 * n; break;
+        default: break;
+        }
+    return bytes;
 }
 
 void Shadow::derive_record(uint32_t i, uint32_t *w) const {
     float p[kMaxParams];
     for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
-    static_assert((int)VCC_N >= (int)DTC_N, "fc holds either kind's float coefficients");
-    float fc[VCC_N];
-    switch (kind) {
-    case OLFX_KIND_DATTORRO:
-        derive_dattorro(p, fc);
-        std::memcpy(w, fc, DTC_N * 4);
-        break;
-    case OLFX_KIND_CHORUS: derive_chorus(p, sr, w); break;
-    case OLFX_KIND_PITCHSHIFT: derive_pitchshift(p, sr, w); break;
-    case OLFX_KIND_CHAIN:
-        derive_chorus(p + OLFX_CN_CHORUS0, sr, w);
-        derive_pitchshift(p + OLFX_CN_PITCH0, sr, w + CHC_N);
-        derive_dattorro(p + OLFX_CN_VERB0, fc);
-        std::memcpy(w + 2 * CHC_N, fc, DTC_N * 4);
-        break;
-    case OLFX_KIND_FXRACK: derive_fxrack(p, sr, w); break;
-    case OLFX_KIND_PLATERACK:
-        derive_fxrack(p + OLFX_PR_RACK0, sr, w);
-        derive_dattorro(p + OLFX_PR_VERB0, fc);
-        std::memcpy(w + FRC_N, fc, DTC_N * 4);
-        break;
-    case OLFX_KIND_VOICE:
-    case OLFX_KIND_VOICE_MOOG:
-    case OLFX_KIND_VOICE_SAMPLE:
-        derive_voice(p, configured[i] != 0, kind == OLFX_KIND_VOICE_MOOG, sr, fc);
-        std::memcpy(w, fc, VCC_N * 4);
-        if (kind == OLFX_KIND_VOICE_SAMPLE) sample_record(i, w + VCC_N);
-        break;
-    case OLFX_KIND_SYNTH:
-    case OLFX_KIND_SYNTH_SVF:
-        derive_voice(p + OLFX_SY_VOICE0, configured[i] != 0, kind == OLFX_KIND_SYNTH, sr, fc);
-        std::memcpy(w, fc, VCC_N * 4);
-        derive_fxrack(p + OLFX_SY_RACK0, sr, w + VCC_N);
-        break;
-    default: break;
+    for (uint32_t j = 0; j < kd->nparts; ++j) {
+        const Component &c = kComponents[kd->parts[j].comp];
+        c.derive(p + kd->parts[j].field0, *this, i, w);
+        w += c.words;
     }
 }
 
@@ -535,21 +556,10 @@ const char *Shadow::bad_value(uint32_t field, float v) const {
     if (!std::isfinite(v)) return "non-finite value";
     // the reference converts value * MAX_PREDELAY (4800) to uint16 (verb.cpp:137-139): values whose
     // product leaves [0, 65536) have no defined meaning there
-    const bool predelay = (kind == OLFX_KIND_DATTORRO && field == OLFX_DT_PREDELAY) ||
-                          (kind == OLFX_KIND_CHAIN && field == OLFX_CN_VERB0 + OLFX_DT_PREDELAY) ||
-                          (kind == OLFX_KIND_PLATERACK && field == OLFX_PR_VERB0 + OLFX_DT_PREDELAY);
-    if (predelay && !(v >= 0.f && v * 4800.0f < 65536.0f)) return "pre-delay outside [0, 65536/4800)";
-    if (kind == OLFX_KIND_FXRACK && field == OLFX_FR_TOPOLOGY && !(v >= 0.f && v <= 4.f && v == (float)(int)v))
-        return "rack topology must be 0, 1, 2, 3 or 4";
-    // the components alone (2..4) are the firmware's objects around the ReverbSc stub: no plate in them
-    if (kind == OLFX_KIND_PLATERACK && field == OLFX_PR_RACK0 + OLFX_FR_TOPOLOGY && !(v == 0.f || v == 1.f))
-        return "plate rack topology must be 0 or 1";
-    // the firmware's callback is the only chain the synth kernel runs
-    if (kind == OLFX_KIND_SYNTH && field == OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY && v != 1.f)
-        return "synth rack topology must be 1";
-    // the Svf synth runs the rack proper (0) as well; the components alone (2..4) have no voices in front
-    if (kind == OLFX_KIND_SYNTH_SVF && field == OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY && !(v == 0.f || v == 1.f))
-        return "svf synth rack topology must be 0 or 1";
+    if (field == kd->pre_field && !(v >= 0.f && v * 4800.0f < 65536.0f)) return "pre-delay outside [0, 65536/4800)";
+    // a whole number 0..4 that the kind's rack runs
+    if (field == kd->topo_field && !(v >= 0.f && v <= 4.f && v == (float)(int)v && (kd->topologies >> (int)v & 1)))
+        return kd->topology_msg;
     return nullptr;
 }
 
@@ -557,9 +567,9 @@ const char *Shadow::bad_value(uint32_t field, float v) const {
 // kernel variant that serves them) follows its topology field.
 void Shadow::store_param(uint32_t field, uint32_t inst, float v) {
     float &slot = params[(size_t)field * n + inst];
-    if (kind == OLFX_KIND_DATTORRO && field == OLFX_DT_PREDELAY) pre_changed = true;
-    if (kind == OLFX_KIND_FXRACK && field == OLFX_FR_TOPOLOGY)
-        n_components += (v >= 2.f ? 1 : 0) - (slot >= 2.f ? 1 : 0);
+    // (only the standalone reverb, the kind without a fixed kernel, picks its network by the pre-delays)
+    if (field == kd->pre_field && !kd->kernel) pre_changed = true;
+    if (field == kd->topo_field) n_components += (v >= 2.f ? 1 : 0) - (slot >= 2.f ? 1 : 0);
     slot = v;
 }
 
@@ -617,7 +627,7 @@ int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
 
 int Shadow::update(uint32_t first, uint32_t count) {
     if ((uint64_t)first + count > n) return fail(OLFX_E_ARG, "olfx_update: range out of bounds");
-    if (takes_note_events(kind))
+    if (kd->takes_note_events())
         for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
     mark_dirty(first, count);
     return OLFX_OK;
@@ -625,7 +635,7 @@ int Shadow::update(uint32_t first, uint32_t count) {
 
 // ---- sample voices ----
 int Shadow::bank_plan(uint32_t n_samples, const uint64_t *offsets, const float *pcm, BankPlan *plan) {
-    if (kind != OLFX_KIND_VOICE_SAMPLE) return fail(OLFX_E_STATE, "olfx_sample_bank: not a sample-voice engine");
+    if (!kd->has_sample) return fail(OLFX_E_STATE, "olfx_sample_bank: not a sample-voice engine");
     plan->base.clear();
     plan->len.clear();
     plan->floats = 0;
@@ -657,7 +667,7 @@ void Shadow::bank_commit(BankPlan &&plan) {
 }
 
 int Shadow::sample_voices(const olfx_sample_voice *recs, uint32_t count) {
-    if (kind != OLFX_KIND_VOICE_SAMPLE) return fail(OLFX_E_STATE, "olfx_sample_voices: not a sample-voice engine");
+    if (!kd->has_sample) return fail(OLFX_E_STATE, "olfx_sample_voices: not a sample-voice engine");
     if (count && !recs) return fail(OLFX_E_ARG, "olfx_sample_voices: null records");
     for (uint32_t k = 0; k < count; ++k) {
         if (recs[k].inst >= n) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: voice out of range", k);
@@ -692,7 +702,8 @@ void Shadow::sample_record(uint32_t i, uint32_t *w) const {
 }
 
 bool Shadow::uniform_predelay() const {
-    const float *pd = params.data() + (size_t)OLFX_DT_PREDELAY * n;
+    if (kd->pre_field == kNoField) return true;
+    const float *pd = params.data() + (size_t)kd->pre_field * n;
     const uint32_t d0 = dattorro_predelay_samples(pd[0]);
     for (uint32_t i = 1; i < n; ++i)
         if (dattorro_predelay_samples(pd[i]) != d0) return false;
@@ -721,87 +732,171 @@ bool is_reverb_cc(uint8_t c) {
 }
 }  // namespace
 
+namespace {
+
+// A control's value as the handlers scale it.  MIDI: ol::core::scale(val, 0, 127, lo, hi, power);
+// hardware: scale(value, 0, 1, ...) or the raw value.
+struct CcValue {
+    bool midi;
+    float value;
+    uint32_t *field;                             // what a table's entry sets, and to what
+    float *param_value;
+    int put(uint32_t f, float v) const { *field = f; *param_value = v; return OLFX_OK; }
+    float sc(float hi, float power) const {
+        return midi ? core_scale(value, 0.f, 127.f, 0.f, hi, power) : core_scale(value, 0.f, 1.f, 0.f, hi, power);
+    }
+    float unit() const { return midi ? core_scale(value, 0.f, 127.f, 0.f, 1.f, 1.f) : value; }   // `scaled` / raw value
+};
+
+// The components' control tables: the reference's handlers, restated.  Each gives the component's own
+// field (or OLFX_FIELD_UPDATE_ONLY) and returns OLFX_OK, or OLFX_IGNORED.
+int voice_cc(uint8_t control, const CcValue &x) {     // SynthVoice.h:100-229
+    switch (control) {
+    case CC_CTL_VOLUME: return x.put(OLFX_VC_AMP_ENV_AMOUNT, x.unit());
+    case CC_CTL_PORTAMENTO: return x.put(OLFX_VC_PORTAMENTO, x.sc(1.f, 4.f));
+    case CC_FILTER_CUTOFF: return x.put(OLFX_VC_FILTER_CUTOFF, x.sc(20000.f, 2.5f));
+    case CC_FILTER_RESONANCE: return x.put(OLFX_VC_FILTER_RESONANCE, x.unit());
+    case CC_FILTER_DRIVE: return x.put(OLFX_VC_FILTER_DRIVE, x.unit());
+    case CC_ENV_FILT_AMT: return x.put(OLFX_VC_FILTER_ENV_AMOUNT, x.unit());
+    case CC_ENV_FILT_A: return x.put(OLFX_VC_FILTER_ATTACK, x.unit());
+    case CC_ENV_FILT_D: return x.put(OLFX_VC_FILTER_DECAY, x.sc(1.f, 3.f));
+    case CC_ENV_FILT_S: return x.put(OLFX_VC_FILTER_SUSTAIN, x.unit());
+    case CC_ENV_FILT_R: return x.put(OLFX_VC_FILTER_RELEASE, x.unit());
+    case CC_ENV_AMP_A: return x.put(OLFX_VC_AMP_ATTACK, x.unit());
+    case CC_ENV_AMP_D: return x.put(OLFX_VC_AMP_DECAY, x.unit());
+    case CC_ENV_AMP_S: return x.put(OLFX_VC_AMP_SUSTAIN, x.unit());
+    case CC_ENV_AMP_R: return x.put(OLFX_VC_AMP_RELEASE, x.unit());
+    case CC_OSC_1_VOLUME: return x.put(OLFX_FIELD_UPDATE_ONLY, x.unit());   // osc_1_mix: unused by Process
+    default: return OLFX_IGNORED;
+    }
+}
+
+// The plate as a rack's reverb: ReverbFx::UpdateMidiControl / UpdateHardwareControl (Fx.h:313-391)
+// composed with the plate glue (ReverbFx.cpp:29-37)
+int reverbfx_cc(uint8_t control, const CcValue &x) {
+    switch (control) {
+    case CC_REVERB_TIME: return x.put(OLFX_DT_DECAY, x.unit());
+    case CC_REVERB_PREFILTER: return x.put(OLFX_DT_PREFILTER, x.unit());
+    case CC_REVERB_INPUT_DIFFUSION_1: return x.put(OLFX_DT_INPUT_DIFFUSION1, x.unit());
+    case CC_REVERB_DECAY_DIFFUSION:
+    case CC_REVERB_INPUT_DIFFUSION_2:          // the reference's quirk (Fx.h:323-324), kept
+        return x.put(OLFX_DT_DECAY_DIFFUSION, x.unit());
+    case CC_REVERB_CUTOFF: return x.put(OLFX_DT_DAMPING, x.unit());   // the 0..1 form (Fx.h:328)
+    case CC_REVERB_PREDELAY:
+    case CC_EARLY_PREDELAY: return x.put(OLFX_FIELD_UPDATE_ONLY, x.unit());   // members the glue never forwards
+    default: return OLFX_IGNORED;
+    }
+}
+
+int rack_cc(uint8_t control, const CcValue &x) {      // FxRack -> FilterFx / DelayFx / ReverbFx
+    switch (control) {
+    case CC_FX_FILTER_CUTOFF: return x.put(OLFX_FR_FILTER_CUTOFF, x.midi ? x.sc(20000.f, 1.f) : x.sc(20000.f, 1.02f));
+    case CC_FX_FILTER_RESONANCE: return x.put(OLFX_FR_FILTER_RESONANCE, x.unit());
+    case CC_FX_FILTER_DRIVE: return x.put(OLFX_FR_FILTER_DRIVE, x.unit());
+    case CC_FX_FILTER_TYPE: return x.put(OLFX_FR_FILTER_TYPE, (float)(int32_t)x.sc(5.f, 1.f));   // FilterType(float)
+    case CC_DELAY_TIME: return x.put(OLFX_FR_DELAY_TIME, x.unit());
+    case CC_DELAY_FEEDBACK: return x.put(OLFX_FR_DELAY_FEEDBACK, x.unit());
+    case CC_DELAY_BALANCE: return x.put(OLFX_FR_DELAY_BALANCE, x.unit());
+    case CC_DELAY_CUTOFF:                      // DelayFx handles these in MIDI only (Fx.h:253-260)
+        return x.midi ? x.put(OLFX_FR_DELAY_CUTOFF, x.sc(20000.f, 1.f)) : OLFX_IGNORED;
+    case CC_DELAY_RESONANCE: return x.midi ? x.put(OLFX_FR_DELAY_RESONANCE, x.unit()) : OLFX_IGNORED;
+    case CC_REVERB_BALANCE: return x.put(OLFX_FR_REVERB_BALANCE, x.unit());
+    case CC_CTL_VOLUME: return x.put(OLFX_FR_MASTER_VOLUME, x.unit());
+    default: return OLFX_IGNORED;              // incl. the reverb CCs that reach only the ReverbSc stub
+    }
+}
+
+// One control through a kind's parts, in order, with its rack at `topology`: the 0 to 2 (field, value)
+// pairs it sets, or an error.  Voices take their controls whatever the topology (handleMidi,
+// ol_daisy/app/synth/main.cpp:201-207: the voices, then delay_fx, reverb_fx, filter_fx).  Topology 0 is
+// FxRack with its own handlers (Fx.h:451-489).  At the others there is no FxRack around the components
+// (main.cpp sends every CC to delay_fx, reverb_fx and filter_fx directly): CC_FILTER_* (41-44) reach a
+// FilterFx's own handler (Fx.h:116-139), which the rack's table reaches as CC_FX_FILTER_* (45-48);
+// FxRack's own CC_FX_FILTER_* and master volume (CC 7) reach nothing.  A component alone (2..4) takes only
+// its own controls: DelayFx 35-39 (Fx.h:218-267), ReverbFx the reverb CCs (of which only the balance, 34,
+// is audible through the ReverbSc stub; a plate behind the rack is its ReverbFx and takes them all),
+// FilterFx 41-44.  A plate without a rack has no handlers.
+int route_control(const KindDesc &kd, uint32_t topology, uint8_t control, int source, float value, uint32_t field[2],
+                  float param_value[2]) {
+    if (!kd.nparts) return OLFX_E_KIND;
+    const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
+    const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
+    const bool has_rack = kd.topo_field != kNoField;
+    int hits = 0;
+    for (uint32_t j = 0; j < kd.nparts; ++j) {
+        const Part &pt = kd.parts[j];
+        uint8_t as = control;
+        if (topology && pt.comp == CP_RACK) {
+            const bool takes = topology == 1u   ? filter_cc || delay_cc || control == CC_REVERB_BALANCE
+                               : topology == 2u ? delay_cc
+                               : topology == 3u ? control == CC_REVERB_BALANCE
+                                                : filter_cc;
+            if (!takes) continue;
+            if (filter_cc) as = (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF);
+        }
+        if (topology && pt.comp == CP_PLATE && !(topology == 1u && is_reverb_cc(control))) continue;
+        if (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE) return OLFX_E_ARG;
+        uint32_t f = 0;
+        float v = 0.f;
+        const CcValue x{source == OLFX_CTL_MIDI, value, &f, &v};
+        int rc = OLFX_IGNORED;
+        if (pt.comp == CP_VOICE) rc = voice_cc(as, x);
+        else if (pt.comp == CP_RACK) rc = rack_cc(as, x);
+        else if (pt.comp == CP_PLATE && has_rack) rc = reverbfx_cc(as, x);
+        if (rc == OLFX_OK && hits < 2) {
+            field[hits] = f == OLFX_FIELD_UPDATE_ONLY ? f : pt.field0 + f;
+            param_value[hits++] = v;
+        }
+    }
+    return hits;
+}
+
+}  // namespace
+
 int Shadow::control(const olfx_control_event *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
-        if (is_synth_kind(kind)) {
-            // handleMidi (main.cpp:201-207): the voices, then delay_fx, reverb_fx, filter_fx; the Svf synth at
-            // topology 0: the voices, then FxRack's own handlers
-            uint32_t fields[2];
-            float vals[2];
-            const float tp = params[(size_t)(OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY) * n + ev[k].inst];
-            const int hits = olfx_synth_control_map_at(kind, (uint32_t)tp, ev[k].control, ev[k].source, ev[k].value,
-                                                       fields, vals);
-            if (hits < 0) return fail(hits, "olfx_control: event %u", k);
-            for (int h = 0; h < hits; ++h) {
-                if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {    // the voices' Update() with unchanged members
-                    configured[ev[k].inst] = 1;
-                    mark_dirty(ev[k].inst, 1);
-                } else if (const int r2 = set_range(ev[k].inst, 1, fields[h], 1, &vals[h])) {
-                    return r2;
-                }
+        const uint32_t topology = kd->topo_field == kNoField ? 0u : (uint32_t)params[(size_t)kd->topo_field * n + ev[k].inst];
+        uint32_t fields[2];
+        float vals[2];
+        const int hits = route_control(*kd, topology, ev[k].control, ev[k].source, ev[k].value, fields, vals);
+        if (hits < 0) return fail(hits, "olfx_control: event %u", k);
+        for (int h = 0; h < hits; ++h) {
+            if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {    // Update() with unchanged members (the voices': now configured)
+                if (kd->takes_note_events()) configured[ev[k].inst] = 1;
+                mark_dirty(ev[k].inst, 1);
+            } else if (const int r2 = set_range(ev[k].inst, 1, fields[h], 1, &vals[h])) {
+                return r2;
             }
-            continue;
         }
-        uint32_t field;
-        float v;
-        uint8_t control = ev[k].control;
-        const float topo = kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK
-                               ? params[(size_t)OLFX_FR_TOPOLOGY * n + ev[k].inst] : 0.f;
-        if (topo != 0.f) {
-            // No FxRack around these instances (ol_daisy/app/synth/main.cpp:201-207 sends every CC to
-            // delay_fx, reverb_fx and filter_fx directly): CC_FILTER_* (41-44) reach a FilterFx's own
-            // handler (Fx.h:116-139), which the rack field map reaches as CC_FX_FILTER_* (45-48);
-            // FxRack's own CC_FX_FILTER_* and master volume (CC 7) reach nothing.  A component alone
-            // takes only its own controls: DelayFx 35-39 (Fx.h:218-267), ReverbFx the reverb CCs (of
-            // which only the balance, 34, is audible through the ReverbSc stub), FilterFx 41-44.
-            const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
-            const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
-            // (the plate rack's ReverbFx takes every reverb CC: the table at OLFX_PR_*)
-            const bool reverb_cc = control == CC_REVERB_BALANCE ||
-                                   (kind == OLFX_KIND_PLATERACK && is_reverb_cc(control));
-            const bool takes = topo == 1.f ? (filter_cc || delay_cc || reverb_cc)
-                             : topo == 2.f ? delay_cc : topo == 3.f ? control == CC_REVERB_BALANCE : filter_cc;
-            if (!takes) continue;
-            if (filter_cc) control = (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF);
-        }
-        const int rc = olfx_control_map(kind, control, ev[k].source, ev[k].value, &field, &v);
-        if (rc == OLFX_IGNORED) continue;
-        if (rc != OLFX_OK) return fail(rc, "olfx_control: event %u", k);
-        if (field == OLFX_FIELD_UPDATE_ONLY) {    // Update() with unchanged members
-            if (is_voice_kind(kind)) configured[ev[k].inst] = 1;
-            mark_dirty(ev[k].inst, 1);
-            continue;
-        }
-        if (const int r2 = set_range(ev[k].inst, 1, field, 1, &v)) return r2;
     }
     return OLFX_OK;
 }
 
 int Shadow::note_events(const olfx_event *ev, uint32_t count) {
-    if (!takes_note_events(kind)) return fail(OLFX_E_STATE, "olfx_note_events: not a voice engine");
+    if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_note_events: not a voice engine");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_note_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_GATE_OFF)
             return fail(OLFX_E_ARG, "olfx_note_events: bad event %u", k);
     }
     for (uint32_t k = 0; k < count; ++k) {
-        if (is_synth_kind(kind)) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        if (instruments()) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         else events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
     }
     return OLFX_OK;
 }
 
 int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
-    if (!takes_note_events(kind)) return fail(OLFX_E_STATE, "olfx_voice_events: not a voice engine");
+    if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_voice_events: not a voice engine");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_voice_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_SET_FREQUENCY ||
             (ev[k].type == OLFX_EV_SET_FREQUENCY && !std::isfinite(ev[k].value)))
             return fail(OLFX_E_ARG, "olfx_voice_events: bad event %u", k);
     }
-    if (is_synth_kind(kind)) {
+    if (instruments()) {
         for (uint32_t k = 0; k < count; ++k) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         return OLFX_OK;
     }
@@ -845,7 +940,7 @@ void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velo
 }
 
 int Shadow::synth_playing(uint32_t inst, uint8_t *out) {
-    if (!is_synth_kind(kind)) return fail(OLFX_E_STATE, "olfx_synth_playing: not a synth engine");
+    if (!instruments()) return fail(OLFX_E_STATE, "olfx_synth_playing: not a synth engine");
     if (inst >= n || !out) return fail(OLFX_E_ARG, "olfx_synth_playing: bad argument");
     for (uint32_t p = 0; p < voices; ++p) out[p] = playing[(size_t)p * n + inst];
     return OLFX_OK;
@@ -878,7 +973,7 @@ float mtof_note(uint8_t note) {
 // GateOn = Seek(0) + Play() and GateOff = Pause() (SampleSoundSource.h:21-26): any NoteOn / GateOn of
 // the block seeks to 0 (VEV_SEEK), and `playing` follows the last gate call like the gate itself.
 void Shadow::fold_events() {
-    const uint32_t seek = kind == OLFX_KIND_VOICE_SAMPLE ? (uint32_t)VEV_SEEK : 0u;
+    const uint32_t seek = kd->has_sample ? (uint32_t)VEV_SEEK : 0u;
     folded.clear();
     for (const olfx_voice_event &ev : events) {
         int32_t &k = ev_slot[ev.inst];
@@ -959,7 +1054,7 @@ size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev) {
 
 void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     const size_t m = dirty_list.size();
-    const uint32_t W = coef_segments(kind).total();
+    const uint32_t W = kd->words;
     uint32_t *val = buf + pl.o_val;
     h_words.resize(W);
     for (size_t r = 0; r < m; ++r) {
@@ -978,111 +1073,36 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
 // =============================================================================================
 // C-ABI: the one entry point that needs no engine
 // =============================================================================================
+// A kind's control table as it stands, without topology routing: its parts' tables (route_control at topology 0)
 extern "C" int olfx_control_map(int kind, uint8_t control, int source, float value, uint32_t *field, float *param_value) {
-    using namespace olfx;
     using namespace olfx::host;
     if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
-    const bool midi = source == OLFX_CTL_MIDI;
-    // MIDI: ol::core::scale(val, 0, 127, lo, hi, power); hardware: scale(value, 0, 1, ...) or raw
-    auto sc = [&](float hi, float power) {
-        return midi ? core_scale(value, 0.f, 127.f, 0.f, hi, power) : core_scale(value, 0.f, 1.f, 0.f, hi, power);
-    };
-    const float unit = midi ? core_scale(value, 0.f, 127.f, 0.f, 1.f, 1.f) : value;   // `scaled` / raw value
-    auto put = [&](uint32_t f, float v) { *field = f; *param_value = v; return OLFX_OK; };
-    if (is_voice_kind(kind)) {                     // SynthVoice.h:100-229
-        switch (control) {
-        case CC_CTL_VOLUME: return put(OLFX_VC_AMP_ENV_AMOUNT, unit);
-        case CC_CTL_PORTAMENTO: return put(OLFX_VC_PORTAMENTO, sc(1.f, 4.f));
-        case CC_FILTER_CUTOFF: return put(OLFX_VC_FILTER_CUTOFF, sc(20000.f, 2.5f));
-        case CC_FILTER_RESONANCE: return put(OLFX_VC_FILTER_RESONANCE, unit);
-        case CC_FILTER_DRIVE: return put(OLFX_VC_FILTER_DRIVE, unit);
-        case CC_ENV_FILT_AMT: return put(OLFX_VC_FILTER_ENV_AMOUNT, unit);
-        case CC_ENV_FILT_A: return put(OLFX_VC_FILTER_ATTACK, unit);
-        case CC_ENV_FILT_D: return put(OLFX_VC_FILTER_DECAY, sc(1.f, 3.f));
-        case CC_ENV_FILT_S: return put(OLFX_VC_FILTER_SUSTAIN, unit);
-        case CC_ENV_FILT_R: return put(OLFX_VC_FILTER_RELEASE, unit);
-        case CC_ENV_AMP_A: return put(OLFX_VC_AMP_ATTACK, unit);
-        case CC_ENV_AMP_D: return put(OLFX_VC_AMP_DECAY, unit);
-        case CC_ENV_AMP_S: return put(OLFX_VC_AMP_SUSTAIN, unit);
-        case CC_ENV_AMP_R: return put(OLFX_VC_AMP_RELEASE, unit);
-        case CC_OSC_1_VOLUME: return put(OLFX_FIELD_UPDATE_ONLY, unit);   // osc_1_mix: unused by Process
-        default: return OLFX_IGNORED;
-        }
-    }
-    if (kind == OLFX_KIND_PLATERACK) {
-        // ReverbFx::UpdateMidiControl / UpdateHardwareControl (Fx.h:313-391) composed with the plate
-        // glue (ReverbFx.cpp:29-37); the rack's other controls below
-        constexpr uint32_t V = OLFX_PR_VERB0;
-        switch (control) {
-        case CC_REVERB_TIME: return put(V + OLFX_DT_DECAY, unit);
-        case CC_REVERB_PREFILTER: return put(V + OLFX_DT_PREFILTER, unit);
-        case CC_REVERB_INPUT_DIFFUSION_1: return put(V + OLFX_DT_INPUT_DIFFUSION1, unit);
-        case CC_REVERB_DECAY_DIFFUSION:
-        case CC_REVERB_INPUT_DIFFUSION_2:          // the reference's quirk (Fx.h:323-324), kept
-            return put(V + OLFX_DT_DECAY_DIFFUSION, unit);
-        case CC_REVERB_CUTOFF: return put(V + OLFX_DT_DAMPING, unit);   // the 0..1 form (Fx.h:328)
-        case CC_REVERB_PREDELAY:
-        case CC_EARLY_PREDELAY: return put(OLFX_FIELD_UPDATE_ONLY, unit);   // members the glue never forwards
-        default: break;
-        }
-    }
-    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK) {   // FxRack -> FilterFx / DelayFx / ReverbFx
-        switch (control) {
-        case CC_FX_FILTER_CUTOFF: return put(OLFX_FR_FILTER_CUTOFF, midi ? sc(20000.f, 1.f) : sc(20000.f, 1.02f));
-        case CC_FX_FILTER_RESONANCE: return put(OLFX_FR_FILTER_RESONANCE, unit);
-        case CC_FX_FILTER_DRIVE: return put(OLFX_FR_FILTER_DRIVE, unit);
-        case CC_FX_FILTER_TYPE: return put(OLFX_FR_FILTER_TYPE, (float)(int32_t)sc(5.f, 1.f));   // FilterType(float)
-        case CC_DELAY_TIME: return put(OLFX_FR_DELAY_TIME, unit);
-        case CC_DELAY_FEEDBACK: return put(OLFX_FR_DELAY_FEEDBACK, unit);
-        case CC_DELAY_BALANCE: return put(OLFX_FR_DELAY_BALANCE, unit);
-        case CC_DELAY_CUTOFF:                      // DelayFx handles these in MIDI only (Fx.h:253-260)
-            return midi ? put(OLFX_FR_DELAY_CUTOFF, sc(20000.f, 1.f)) : OLFX_IGNORED;
-        case CC_DELAY_RESONANCE: return midi ? put(OLFX_FR_DELAY_RESONANCE, unit) : OLFX_IGNORED;
-        case CC_REVERB_BALANCE: return put(OLFX_FR_REVERB_BALANCE, unit);
-        case CC_CTL_VOLUME: return put(OLFX_FR_MASTER_VOLUME, unit);
-        default: return OLFX_IGNORED;              // incl. the reverb CCs that reach only the ReverbSc stub
-        }
-    }
+    const KindDesc &kd = kind_desc(kind);
     // the synths' controls can hit two fields: olfx_synth_control_map / olfx_synth_control_map_at
-    return n_params_of(kind) && !is_synth_kind(kind) ? OLFX_IGNORED : OLFX_E_KIND;
+    if (kd.instances == KindDesc::INSTRUMENTS) return OLFX_E_KIND;
+    uint32_t f[2];
+    float v[2];
+    const int hits = route_control(kd, 0u, control, source, value, f, v);
+    if (hits <= 0) return hits ? hits : OLFX_IGNORED;
+    *field = f[0];
+    *param_value = v[0];
+    return OLFX_OK;
 }
 
-// handleMidi's fan-out (main.cpp:201-207), from the two kinds' tables above: the voices' handler, then
-// the rack's at topology 1 as Shadow::control routes it (DelayFx 35-39, ReverbFx's balance 34 -- its
-// other controls reach only the ReverbSc stub --, FilterFx 41-44 through the rack's 45-48 entries)
+// handleMidi's fan-out (main.cpp:201-207): the voices' handler, then the rack's at topology 1 as
+// olfx_control routes it (route_control)
 extern "C" int olfx_synth_control_map(uint8_t control, int source, float value, uint32_t field[2], float param_value[2]) {
     return olfx_synth_control_map_at(OLFX_KIND_SYNTH, 1u, control, source, value, field, param_value);
 }
 
-// The same for either synth kind at a rack topology: the kind's voice table, then the rack's as
-// Shadow::control routes an OLFX_KIND_FXRACK instance of that topology -- 1 as above, 0 FxRack's own
-// UpdateMidiControl / UpdateHardwareControl (the rack's table as it stands: 45-48 the filter, 7 the master)
+// The same for either synth kind at a rack topology the kind accepts: the kind's voice table, then the
+// rack's as olfx_control routes an OLFX_KIND_FXRACK instance of that topology
 extern "C" int olfx_synth_control_map_at(int kind, uint32_t topology, uint8_t control, int source, float value,
                                          uint32_t field[2], float param_value[2]) {
-    using namespace olfx;
     using namespace olfx::host;
-    if (!is_synth_kind(kind)) return OLFX_E_KIND;
+    const KindDesc &kd = kind_desc(kind);
+    if (kd.instances != KindDesc::INSTRUMENTS) return OLFX_E_KIND;
     if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
-    if (topology > 1u || (kind == OLFX_KIND_SYNTH && topology != 1u)) return OLFX_E_ARG;
-    int hits = 0;
-    uint32_t f;
-    float v;
-    int rc = olfx_control_map(kind == OLFX_KIND_SYNTH ? OLFX_KIND_VOICE_MOOG : OLFX_KIND_VOICE, control, source, value, &f, &v);
-    if (rc < 0) return rc;
-    if (rc == OLFX_OK) {
-        field[hits] = f == OLFX_FIELD_UPDATE_ONLY ? f : OLFX_SY_VOICE0 + f;
-        param_value[hits++] = v;
-    }
-    const bool filter_cc = control >= CC_FILTER_CUTOFF && control <= CC_FILTER_DRIVE;
-    const bool delay_cc = control >= CC_DELAY_TIME && control <= CC_DELAY_BALANCE;
-    if (topology == 0u || filter_cc || delay_cc || control == CC_REVERB_BALANCE) {
-        const uint8_t as = topology == 1u && filter_cc ? (uint8_t)(control - CC_FILTER_CUTOFF + CC_FX_FILTER_CUTOFF) : control;
-        rc = olfx_control_map(OLFX_KIND_FXRACK, as, source, value, &f, &v);
-        if (rc < 0) return rc;
-        if (rc == OLFX_OK) {
-            field[hits] = OLFX_SY_RACK0 + f;
-            param_value[hits++] = v;
-        }
-    }
-    return hits;
+    if (topology > 4u || !(kd.topologies >> topology & 1)) return OLFX_E_ARG;
+    return route_control(kd, topology, control, source, value, field, param_value);
 }

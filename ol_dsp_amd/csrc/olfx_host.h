@@ -1,5 +1,5 @@
 // ol_dsp_amd/csrc/olfx_host.h -- the host's control logic that touches neither the GPU nor a HIP
-// type: the kind tables, the reference's setter arithmetic (parameters -> coefficient words), the
+// type: the kind table, the reference's setter arithmetic (parameters -> coefficient words), the
 // host shadow of an engine's parameters with its validation and bookkeeping, and the format of the
 // control packet.  olfx_engine.cpp owns a Shadow by value and delivers the packets it fills;
 // tests/cpp/test_host_core.cpp drives the same code on the CPU.
@@ -15,7 +15,39 @@
 namespace olfx {
 namespace host __attribute__((visibility("hidden"))) {
 
-// ---- per-kind tables ----
+// ---- components and kinds (the table is in olfx_host.cpp) ----
+// A component is the unit that has parameters, defaults, a setter restatement and a coefficient block.
+enum Comp : uint8_t { CP_PLATE, CP_CHORUS, CP_PITCH, CP_VOICE, CP_RACK, CP_SAMPLE, CP_COUNT };
+// The engine's coefficient arrays (olfx_engine.cpp gives each its pointer and stride).
+enum Dst : uint8_t { TO_DT, TO_CH, TO_PS, TO_VC, TO_FR, TO_SM, TO_COUNT };
+// A component of a kind: where its parameters start in the kind's fields, where its coefficients go.
+struct Part { Comp comp; uint8_t field0; Dst dst; };
+constexpr uint32_t kNoField = 0xFFFFFFFFu;
+struct KindDesc {
+    uint32_t nparts = 0;                         // 0: not a kind
+    Part parts[3] = {};                          // in record order
+    // what the parts add up to: the kind's fields and record words; a plate part's pre-delay field and a
+    // rack part's topology field (kNoField: no such part); a voice part's fields; whether there is a Sample
+    uint32_t n_params = 0, words = 0, pre_field = kNoField, topo_field = kNoField, voice0 = 0, voice_end = 0;
+    bool has_sample = false;
+    uint32_t nset = 0;
+    struct { uint8_t field; float value; } set[5] = {};   // defaults that differ from the parts' own
+    uint8_t in_ch = 2, out_ch = 2;
+    enum : uint8_t { EFFECTS, VOICES, INSTRUMENTS } instances = EFFECTS;   // INSTRUMENTS: of several voices each
+    bool moog = false;                           // the voice's filter: MoogFilter (VCS_N_MOOG state slots) or Svf
+    uint8_t topologies = 0;                      // bit t: the rack part accepts OLFX_FR_TOPOLOGY t
+    const char *topology_msg = nullptr;          // why not, otherwise
+    double bytes_per_frame = 0.0, read_bytes_per_frame = 0.0;
+    const char *kernel = nullptr;                // null: the standalone reverb's, which follows its pre-delays
+    bool planes_32bit = false;                   // the kernel addresses the audio planes with 32-bit offsets
+    bool pad_plate = false;                      // the plate runs n rounded up to 64 instances
+    bool state_counts_padding = false;           // ... and state_bytes counts them (the chain's figure does not)
+
+    bool takes_note_events() const { return instances != EFFECTS; }
+};
+const KindDesc &kind_desc(int kind);             // an empty row (nparts = 0) for a number that is no kind
+
+// ---- per-kind figures, read from the table ----
 uint32_t n_params_of(int kind);              // 0: unknown kind
 uint32_t in_channels(int kind);
 uint32_t out_channels(int kind);
@@ -23,7 +55,7 @@ void default_params(int kind, float *p);     // the reference's defaults of the 
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize);
 uint64_t state_bytes(int kind, uint32_t n, float sr);      // the synth kinds: the 4-voice figure
 // kinds that take note events (the voices, and the synth through its Polyvoice router)
-inline bool takes_note_events(int kind) { return is_voice_kind(kind) || is_synth_kind(kind); }
+bool takes_note_events(int kind);
 constexpr uint32_t kSynthDefaultVoices = 4, kSynthMaxVoices = 8;
 double algorithmic_bytes_per_frame(int kind);
 double algorithmic_read_bytes_per_frame(int kind);
@@ -31,11 +63,11 @@ double algorithmic_read_bytes_per_frame(int kind);
 // ---- the reference setters: parameters [OLFX_*] -> coefficient words [*C_*] ----
 float core_scale(float in, float inlow, float inhigh, float outlow, float outhigh, float power);
 uint32_t dattorro_predelay_samples(float v);
-void derive_dattorro(const float *p, float *c);
+void derive_dattorro(const float *p, uint32_t *c);
 void derive_chorus(const float *p, double sr, uint32_t *c);
 void derive_pitchshift(const float *p, double sr, uint32_t *c);
 void derive_fxrack(const float *p, float sr, uint32_t *c);
-void derive_voice(const float *p, bool configured, bool moog, float sr, float *c);
+void derive_voice(const float *p, bool configured, bool moog, float sr, uint32_t *c);
 
 // An instance's coefficient record: the words of each destination array (field-major on the
 // device, CoefScatterArgs), in record order.
@@ -79,6 +111,7 @@ struct SampleAsg {
 // an OLFX_E_* code with the reason in `msg`, and a refused call changes nothing.
 struct Shadow {
     int kind = 0;
+    const KindDesc *kd = &kind_desc(0);   // the kind's row, looked up once (init)
     uint32_t n = 0, n_params = 0;
     float sr = 48000.f;
     std::vector<float> params;            // [n_params][n]
@@ -107,13 +140,14 @@ struct Shadow {
     char msg[160] = "";
 
     void init(int kind_, uint32_t n_, float sr_, uint32_t voices_ = kSynthDefaultVoices) {
-        kind = kind_; n = n_; sr = sr_; n_params = n_params_of(kind_);
-        samples.assign(kind_ == OLFX_KIND_VOICE_SAMPLE ? n_ : 0u, SampleAsg{});
-        voices = is_synth_kind(kind_) ? voices_ : 0u;
-        npad = is_synth_kind(kind_) ? (n_ + 63u) & ~63u : 0u;
+        kind = kind_; n = n_; sr = sr_; kd = &kind_desc(kind_); n_params = kd->n_params;
+        samples.assign(kd->has_sample ? n_ : 0u, SampleAsg{});
+        voices = instruments() ? voices_ : 0u;
+        npad = instruments() ? (n_ + 63u) & ~63u : 0u;
     }
+    bool instruments() const { return kd->instances == KindDesc::INSTRUMENTS; }
     // the voice slots that note events address: the instances themselves, or the synth's voices
-    uint32_t n_ev() const { return is_synth_kind(kind) ? voices * npad : n; }
+    uint32_t n_ev() const { return instruments() ? voices * npad : n; }
     // Every instance at the reference's defaults, unconfigured, all dirty; nothing queued.
     void reset();
 
@@ -140,7 +174,7 @@ struct Shadow {
     // The queued events as one record per voice (`folded`) and their place in the event section.
     void fold_events();
     PacketPlan plan(bool evs) const {
-        return plan_packet(n, dirty_list.size(), coef_segments(kind).total(), evs, n_more, n_ev());
+        return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev());
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
@@ -156,7 +190,7 @@ private:
     void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
-        return is_voice_kind(kind) || (is_synth_kind(kind) && n_fields && field0 < OLFX_SY_RACK0);
+        return kd->instances == KindDesc::VOICES || (n_fields && field0 < kd->voice_end && field0 + n_fields > kd->voice0);
     }
 };
 
