@@ -481,6 +481,10 @@ double   olfx_algorithmic_bytes_per_frame(const olfx_engine *e);
    north star's "HBM-read roofline", SURVEY.md section 8d "read-only variant"). */
 double   olfx_algorithmic_read_bytes_per_frame(const olfx_engine *e);
 const char *olfx_kernel_name(const olfx_engine *e);
+/* OLFX_KIND_CHORUS: 1 if the next olfx_process would run the ring-free kernel (chorus_block_rf1: the
+   pitch-shifter's past output rebuilt from the input ring), 0 if the ring kernel olfx_kernel_name
+   reports (while a pitch or window change is younger than the chorus history); -1 for other kinds. */
+int      olfx_chorus_ring_free(const olfx_engine *e);
 const char *olfx_last_error(const olfx_engine *e);   /* e may be NULL: last global error */
 
 #ifdef __cplusplus

@@ -87,6 +87,7 @@ public:
     uint32_t size() const { return olfx_num_instances(e_); }
     uint64_t frames_processed() const { return olfx_frames_processed(e_); }
     const char *kernel_name() const { return olfx_kernel_name(e_); }
+    int chorus_ring_free() const { return olfx_chorus_ring_free(e_); }
 
     void set(uint32_t inst, uint32_t field, float v) {
         check(olfx_set_param(e_, inst, field, v), e_, "olfx_set_param");

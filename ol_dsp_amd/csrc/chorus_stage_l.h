@@ -136,7 +136,7 @@ struct ChStageL {
     uint64_t lfo_acc, ps_acc;
     float z1, z2;
     uint32_t pmask, cmask, pshift, cshift;   // ring sizes are powers of two: instance offset = i << shift
-    uint32_t pmaxu;                          // delay clamps: psize - 2, csize - 2
+    uint32_t pmaxu;                          // delay clamps: ChorusArgs::pmax, csize - 2
     double cmaxd;
     Rsrc rP, rC;
     float *region;
@@ -172,7 +172,7 @@ struct ChStageL {
         z1 = __uint_as_float(a.state[(ch ? CHS_Z1R : CHS_Z1L) * n + i]);
         z2 = __uint_as_float(a.state[(ch ? CHS_Z2R : CHS_Z2L) * n + i]);
         pmask = a.psize - 1u; cmask = a.csize - 1u;
-        pmaxu = a.psize - 2u; cmaxd = (double)(a.csize - 2u);
+        pmaxu = a.pmax; cmaxd = (double)(a.csize - 2u);
         rP = rsrc(a.pitch_ring, (uint64_t)n * 2 * a.psize * 4);
         rC = rsrc(a.chorus_ring, (uint64_t)n * 2 * a.csize * 4);
         pshift = (uint32_t)__builtin_ctz(a.psize) + 3u; cshift = (uint32_t)__builtin_ctz(a.csize) + 3u;

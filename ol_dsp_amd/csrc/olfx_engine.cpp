@@ -125,6 +125,7 @@ struct olfx_engine {
 
     // chorus / pitch-shift (also the chain's first two stages)
     uint32_t psize = 0, csize = 0;
+    uint32_t pmax = 0;           // the pitch delay clamp: the pitch window's bound, whatever psize (ChorusArgs::pmax)
     float *ch_pring = nullptr, *ch_cring = nullptr;
     uint32_t *ch_state = nullptr, *ch_coef = nullptr;
     float *ps_pring = nullptr, *ps_cring = nullptr;      // chain stage 2
@@ -302,6 +303,23 @@ int grow_slot(olfx_engine *e, olfx_engine::Slot &sl, size_t words, bool device_h
     return OLFX_OK;
 }
 
+// The chorus kind's arrays and geometry for a launch whose first frame is the engine's next.
+ChorusArgs chorus_args(const olfx_engine *e, uint32_t n_frames, uint64_t plane) {
+    ChorusArgs a{};
+    a.pitch_ring = e->ch_pring;
+    a.chorus_ring = e->ch_cring;
+    a.state = e->ch_state;
+    a.coef = e->ch_coef;
+    a.plane = plane;
+    a.n = e->n;
+    a.n_frames = n_frames;
+    a.t0 = (uint32_t)(e->frames & 0xFFFFFFFFu);
+    a.psize = e->psize;
+    a.csize = e->csize;
+    a.pmax = e->pmax;
+    return a;
+}
+
 // This block's control packet -- the changed instances' coefficient records and the folded note
 // events (host::PacketPlan) -- in a pinned host slot that the block's kernels read directly over
 // the host link (zero-copy: no copy command, no second stream, no host wait on the device).  The
@@ -350,6 +368,13 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     uint32_t *const dev = copy ? sl.d : sl.hd;      // what the kernels read
     lap(2);
     hs.fill_records(pl, sl.h);
+    if (hs.rf_materialise) {
+        // a pitch or window change ends ring-free mode: the chorus ring's history from the x ring, under
+        // the coefficients still on the device (ahead of the scatter below)
+        hs.rf_materialise = false;
+        const hipError_t r = launch_chorus_materialise(chorus_args(e, 0, 0), hs.rf.depth, s);
+        if (r != hipSuccess) return e->hip_fail(r, "chorus ring materialise launch");
+    }
     lap(3);
     if (evs) hs.write_events(sl.h + pl.o_ev);
     if (copy) {
@@ -489,6 +514,7 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.t0 = t0;
         a.psize = e->psize;
         a.csize = e->csize;
+        a.pmax = e->pmax;
         a.mode = mode;
         return a;
     };
@@ -510,9 +536,13 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_dattorro(dt_args(din, dout), e->dt_net, s);
         break;
     }
-    case OLFX_KIND_CHORUS:
-        r = launch_chorus(ch_args(e->ch_pring, e->ch_cring, e->ch_state, e->ch_coef, din, dout, 0), s);
+    case OLFX_KIND_CHORUS: {
+        // ring-free unless a pitch or window change is younger than the chorus history (host::RingFree)
+        const ChorusArgs a = ch_args(e->ch_pring, e->ch_cring, e->ch_state, e->ch_coef, din, dout, 0);
+        r = e->hs.rf.active() ? launch_chorus_ringfree(a, s) : launch_chorus(a, s);
+        e->hs.rf.advance(n_frames);
         break;
+    }
     case OLFX_KIND_PITCHSHIFT:
         r = launch_chorus(ch_args(e->ch_pring, e->ch_cring, e->ch_state, e->ch_coef, din, dout, 1), s);
         break;
@@ -754,6 +784,9 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     if (const char *cb = std::getenv("OLFX_COPY_BYTES"))
         e->copy_bytes = std::min<size_t>((size_t)std::strtoull(cb, nullptr, 10), olfx_engine::kCopyBytes);
     host::chorus_sizes(sample_rate, &e->psize, &e->csize);
+    e->pmax = e->psize - 2u;
+    // the chorus kind's x ring also holds the chorus history (chorus_stage_rf.h)
+    if (kind == OLFX_KIND_CHORUS) e->psize = host::chorus_x_size(sample_rate);
     e->n_dt = e->hs.kd->pad_plate ? (n_inst + 63u) & ~63u : n_inst;
 
     hipError_t r = hipSetDevice(device);
@@ -1102,6 +1135,11 @@ const char *olfx_kernel_name(const olfx_engine *e) {
     if (!e) return "";
     // the standalone reverb's: the network of the last block (dattorro.hip dattorro_network)
     return e->hs.kd->kernel ? e->hs.kd->kernel : dattorro_network_name(e->dt_net);
+}
+
+int olfx_chorus_ring_free(const olfx_engine *e) {
+    if (!e || e->kind != OLFX_KIND_CHORUS) return -1;
+    return e->hs.ring_free_next() ? 1 : 0;
 }
 
 const char *olfx_last_error(const olfx_engine *e) {

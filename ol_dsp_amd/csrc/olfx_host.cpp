@@ -126,6 +126,16 @@ void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize) {
     *csize = pow2_at_least(2u * (uint32_t)std::ceil(12.0 * sr / 1000.0) + 2);
 }
 
+uint32_t chorus_history(float sr) { return 2u * (uint32_t)std::ceil(12.0 * sr / 1000.0) + 2u; }
+uint32_t chorus_x_size(float sr) {
+    // the oldest x a ring-free launch reads lies the chorus's largest delay, the psv window's tail, the
+    // pitch delay clamp + 1 and a line's 15 positions back, while the next chunk's input (up to 31
+    // positions ahead) is already stored: 64 covers those
+    uint32_t ps, cs;
+    chorus_sizes(sr, &ps, &cs);
+    return pow2_at_least(chorus_history(sr) - 2u + (ps - 2u) + 64u);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Coefficient derivation (control rate, host).  These restate the reference setters.
 // ---------------------------------------------------------------------------------------------
@@ -541,6 +551,9 @@ void Shadow::reset() {
     dirty_list.clear();
     dirty_mark.assign(n, 0);
     mark_dirty(0, n);                        // every coefficient is derived at the first block
+    rf.reset();
+    rf_materialise = false;
+    pitch_sent.assign(kind == OLFX_KIND_CHORUS ? (size_t)4 * n : 0u, 0u);
 }
 
 void Shadow::mark_dirty(uint32_t first, uint32_t count) {
@@ -1052,19 +1065,42 @@ size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev) {
     return n + W * n + ev + 16;
 }
 
+// the words psv depends on (chorus_stage_rf.h): the pitch phasor's increment and the window
+static const uint32_t kPitchWords[4] = {CHC_PS_INC, CHC_PS_INC_LO, CHC_WINDOW, CHC_WINDOW_LO};
+
+bool Shadow::ring_free_next() const {
+    if (kind != OLFX_KIND_CHORUS || !rf.active()) return false;
+    if (!rf.seen) return true;
+    std::vector<uint32_t> w(kd->words);
+    for (const uint32_t i : dirty_list) {
+        derive_record(i, w.data());
+        for (uint32_t k = 0; k < 4; ++k)
+            if (w[kPitchWords[k]] != pitch_sent[(size_t)k * n + i]) return false;
+    }
+    return true;
+}
+
 void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     const size_t m = dirty_list.size();
     const uint32_t W = kd->words;
     uint32_t *val = buf + pl.o_val;
     h_words.resize(W);
+    bool pitch_changed = false;
     for (size_t r = 0; r < m; ++r) {
         const uint32_t i = pl.dense ? (uint32_t)r : dirty_list[r];
         if (!pl.dense) buf[pl.o_inst + r] = i;
         derive_record(i, h_words.data());
+        if (kind == OLFX_KIND_CHORUS)
+            for (uint32_t k = 0; k < 4; ++k) {
+                uint32_t &sent = pitch_sent[(size_t)k * n + i];
+                pitch_changed |= sent != h_words[kPitchWords[k]];
+                sent = h_words[kPitchWords[k]];
+            }
         for (uint32_t w = 0; w < W; ++w) val[(size_t)w * m + r] = h_words[w];
     }
     for (const uint32_t i : dirty_list) dirty_mark[i] = 0;
     dirty_list.clear();
+    if (pitch_changed && rf.changed()) rf_materialise = true;
 }
 
 }  // namespace host

@@ -53,6 +53,11 @@ uint32_t in_channels(int kind);
 uint32_t out_channels(int kind);
 void default_params(int kind, float *p);     // the reference's defaults of the user-facing parameters
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize);
+// The chorus kind's history: the frames of pitch-shifter output its tap can reach (the chorus's
+// largest delay + 2), and the depth of its x ring, which holds that history's own pitch windows too
+// (chorus_stage_rf.h).  The pitch-shift kind and the chain keep chorus_sizes' psize.
+uint32_t chorus_history(float sr);
+uint32_t chorus_x_size(float sr);
 uint64_t state_bytes(int kind, uint32_t n, float sr);      // the synth kinds: the 4-voice figure
 // kinds that take note events (the voices, and the synth through its Polyvoice router)
 bool takes_note_events(int kind);
@@ -106,6 +111,32 @@ struct SampleAsg {
     uint32_t gen = 1;                     // bumped whenever the voice gets a fresh Sample object
 };
 
+// Which kernel the chorus kind runs (chorus_stage_rf.h).  The ring-free kernel recomputes the
+// pitch-shifter's past output from the x ring under the CURRENT pitch and window coefficients, so it
+// may run only while those have been in force for every instance over the whole history; after a
+// change the engine fills the chorus ring from the x ring under the old coefficients (materialise)
+// and runs the ring kernel until `depth` frames have passed.  A change before the first frame since
+// create / reset does not count: all history is zero then, and psv of zeros is +0 under any coefficients.
+struct RingFree {
+    uint32_t depth = 0;                   // chorus_history
+    uint64_t seen = 0;                    // frames since create / reset
+    uint64_t quiet = 0;                   // frames since the last change, saturating at depth
+    void reset() { seen = 0; quiet = depth; }
+    bool active() const { return quiet >= depth; }
+    // a pitch or window word changed ahead of the next block: whether the chorus ring must be
+    // materialised first (it is already current while the ring kernel runs)
+    bool changed() {
+        if (!seen) return false;
+        const bool materialise = active();
+        quiet = 0;
+        return materialise;
+    }
+    void advance(uint32_t n_frames) {
+        seen += n_frames;
+        quiet = quiet + n_frames < depth ? quiet + n_frames : depth;
+    }
+};
+
 // The host shadow of an engine: what the caller has set, what of it the device has yet to see, and
 // the note events queued for the next block.  Every operation that can refuse returns OLFX_OK or
 // an OLFX_E_* code with the reason in `msg`, and a refused call changes nothing.
@@ -137,10 +168,17 @@ struct Shadow {
     // slot p * npad + i of the event queue (SynthArgs, olfx_internal.h)
     uint32_t voices = 0, npad = 0;
     std::vector<uint8_t> playing;
+    // the chorus kind: its kernel switch, the pitch and window words each instance's device coefficients
+    // hold ([4][n]: what fill_records last delivered), and whether the packet just filled asks for the
+    // chorus ring to be materialised ahead of its scatter (the engine clears it)
+    RingFree rf;
+    std::vector<uint32_t> pitch_sent;
+    bool rf_materialise = false;
     char msg[160] = "";
 
     void init(int kind_, uint32_t n_, float sr_, uint32_t voices_ = kSynthDefaultVoices) {
         kind = kind_; n = n_; sr = sr_; kd = &kind_desc(kind_); n_params = kd->n_params;
+        rf.depth = kind_ == OLFX_KIND_CHORUS ? chorus_history(sr_) : 0u;
         samples.assign(kd->has_sample ? n_ : 0u, SampleAsg{});
         voices = instruments() ? voices_ : 0u;
         npad = instruments() ? (n_ + 63u) & ~63u : 0u;
@@ -178,6 +216,10 @@ struct Shadow {
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
+    // The chorus kind: whether the next block runs the ring-free kernel -- the switch's state unless a
+    // dirty instance's pitch or window words differ from the delivered ones (the words, not the call:
+    // setting the same value is no change)
+    bool ring_free_next() const;
     // The folded records into the event section `fix` (buf + o_ev).
     void write_events(uint32_t *fix);
 

@@ -211,6 +211,9 @@ struct ChorusArgs {
     uint32_t t0;                // write position of the first frame (mod ring sizes)
     uint32_t psize, csize;      // ring sizes (powers of two)
     uint32_t mode;              // 0 = full chorus, 1 = pitch-shift stage only
+    // the pitch delay clamp [1, pmax]: the pitch window's own bound (host::chorus_sizes' psize - 2),
+    // whatever the depth of the x ring (the chorus kind's also holds the chorus history)
+    uint32_t pmax;
 };
 
 // ----------------------------------------------------------------------------------------------
@@ -320,6 +323,12 @@ hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
 hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_chorus(const ChorusArgs &a, hipStream_t s);
+// The chorus kind (mode 0) without its chorus ring (chorus_stage_rf.h): valid while every instance's
+// pitch and window coefficients have been in force for the whole chorus history (host::RingFree).
+hipError_t launch_chorus_ringfree(const ChorusArgs &a, hipStream_t s);
+// The last `history` positions of the chorus ring from the x ring, the phasors in a.state and the
+// coefficients in a.coef (a.t0 = the next write position): the switch from ring-free to ring mode.
+hipError_t launch_chorus_materialise(const ChorusArgs &a, uint32_t history, hipStream_t s);
 hipError_t launch_voice(const VoiceArgs &a, hipStream_t s);
 hipError_t launch_sampler(const VoiceArgs &a, hipStream_t s);
 

@@ -374,6 +374,11 @@ class Engine:
     def kernel_name(self) -> str:
         return self.lib.olfx_kernel_name(self._h).decode()
 
+    @property
+    def chorus_ring_free(self) -> int:
+        """The chorus kind: 1 if the next block runs the ring-free kernel, 0 the ring kernel; else -1."""
+        return int(self.lib.olfx_chorus_ring_free(self._h))
+
 
 def control_map(kind, control: int, value: float, source: str = "midi"):
     """The reference's UpdateMidiControl / UpdateHardwareControl mapping for one control change
