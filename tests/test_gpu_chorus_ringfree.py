@@ -5,67 +5,15 @@ CPU oracle's chorus bank, the checker of test_gpu_parity.py.
 Shapes: n = 33 (per-lane I/O, ragged second wave), 36 (row I/O, ragged), 64 (row I/O, two full waves).
 Every case runs at least 2,304 frames: more than the 1,154-frame chorus history plus the 480-frame
 pitch window, so every psv the tap reads has been recomputed from wrapped ring data.  The drawn
-parameters carry fixed columns (COLUMNS) that reach the kernel's edges."""
+parameters carry fixed columns (chorus_support.COLUMNS) that reach the kernel's edges."""
 import numpy as np
 import pytest
 
 import oracle as O
-from helpers import bits_equal, chorus_params, fast_noise, first_mismatch
+from chorus_support import DEPTH, HISTORY, PITCH, WINDOW, apply, draw, run
+from helpers import bits_equal, fast_noise, first_mismatch
 
 pytestmark = pytest.mark.gpu
-
-PITCH, PHASE, DEPTH, RATE, WINDOW = 0, 4, 5, 6, 7
-HISTORY = 1154                      # frames the ring kernel runs after a pitch / window change (48 kHz)
-
-# instance -> {field: value}.  The LFO advances 0.5 Hz / 48 kHz = 1.04e-5 cycle per frame at rate 1:
-# a phase offset just below 1/2 (or 1) makes the delay pass its minimum 0 (or its maximum) mid-run.
-COLUMNS = {
-    0: {DEPTH: 0.08, RATE: 1.0, PHASE: 0.488},     # delay through 0: psv of the current chunk's own frames
-    1: {DEPTH: 1.0, PHASE: 0.0},                    # delay 1,152, the largest
-    2: {PITCH: 0.0},                                # unit ratio: the pitch windows advance exactly one line
-    3: {PITCH: 3.0},                                # fastest advance: two-line steps and phasor wraps
-    4: {DEPTH: 1.0, RATE: 1.0, PHASE: 0.75},        # the fastest delay sweep (|d'| = 0.038 frame / frame)
-    5: {DEPTH: 1.0, RATE: 1.0, PHASE: 0.994},       # delay through its maximum mid-run
-    6: {DEPTH: 0.08, PITCH: 3.0, WINDOW: 10.0, PHASE: 0.5},   # delay 0 with the longest pitch window
-    7: {PITCH: 3.0, WINDOW: 4.0},
-}
-
-
-def draw(n, seed):
-    p = chorus_params(np.random.default_rng(seed), n)
-    for i, col in COLUMNS.items():
-        for f, v in col.items():
-            p[f, i] = v
-    return p
-
-
-def apply(e, ref, p):
-    n = p.shape[1]
-    e.set_params(0, p)
-    for i in range(n):
-        for f in range(8):
-            ref.set(i, f, float(p[f, i]))
-
-
-def run(e, ref, x, blocks, cuda, events=None):
-    """Block by block through the engine; events[b] = [(inst, field, value), ...] applied to the engine
-    and the oracle ahead of block b.  Returns the engine's output, the oracle's, and the mode the
-    engine reported ahead of each block (after that block's sets)."""
-    import torch
-    events = events or {}
-    outs, refs, modes = [], [], []
-    f0 = 0
-    for b, frames in enumerate(blocks):
-        for inst, field, value in events.get(b, []):
-            e.set_param(inst, field, value)
-            ref.set(inst, field, float(value))
-        modes.append(e.chorus_ring_free)
-        xh = np.ascontiguousarray(x[:, f0:f0 + frames])
-        outs.append(e.process(torch.from_numpy(xh).to(cuda)).cpu().numpy())
-        refs.append(ref.process(xh, threads=8))
-        f0 += frames
-    torch.cuda.synchronize()
-    return np.concatenate(outs, axis=1), np.concatenate(refs, axis=1), modes
 
 
 def engine(n):

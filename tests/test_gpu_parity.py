@@ -436,12 +436,15 @@ def test_chorus_golden(cuda, golden, kind, mode):
 
 @pytest.mark.parametrize("n", [1, 200])
 def test_chorus_vs_oracle(cuda, n):
+    """The chorus kind from a pitch set before the first frame: chorus_block_rf1 (the ring-free stage)
+    from frame 0 to the end.  chorus_block_v11<FULL> after a pitch or window change is
+    test_gpu_chorus_ringfree.py's and test_gpu_chorus_modes.py's."""
     rng = np.random.default_rng(100 + n)
     p = chorus_params(rng, n)
     x = fast_noise(n, 4096, seed=n + 1)
     e = engine("chorus", n)
     e.set_params(0, p)
-    y = run_gpu(e, x, [256] * 7 + [4, 12, 240, 2048], cuda)   # tails exercise chorus_tail
+    y = run_gpu(e, x, [256] * 7 + [4, 12, 240, 2048], cuda)   # tails: partial chunks, the generic path
     ref = O.Chorus(n)
     for i in range(n):
         for f in range(8):
@@ -453,7 +456,10 @@ def test_chorus_vs_oracle(cuda, n):
 @pytest.mark.parametrize("kind", ["chorus", "pitchshift"])
 def test_chorus_line_carry_stress(cuda, kind):
     """Extreme depth/rate/pitch/window corners over 64 blocks: every tap window mode (carried
-    line, fresh reload, chorus straggler, pitch-phasor wrap) occurs many times; bit-exact."""
+    line, fresh reload, chorus straggler, pitch-phasor wrap) occurs many times; bit-exact.  The
+    pitch-shift kind runs chorus_block_v11; the chorus kind, its pitch set before the first frame, runs
+    chorus_block_rf1 throughout (the same draw on chorus_block_v11<FULL>:
+    test_gpu_chorus_modes.test_ring_mode_held_blocks_with_tails)."""
     n, frames = 96, 256 * 64
     rng = np.random.default_rng(77)
     p = np.empty((8, n), np.float32)
@@ -487,8 +493,10 @@ def test_chorus_line_carry_stress(cuda, kind):
 def test_chorus_long_run_many_wraps(cuda, kind, n):
     """100,000 frames at the fastest pitch phasors (every instance's two pitch taps wrap 12 times,
     each wrap a generic chunk with direct ring reads), ragged blocks with partial chunks:
-    bit-exact against the oracle.  n = 70 runs chorus_block_v11's per-lane I/O (rows need
-    n % 4 == 0), n = 72 its row I/O."""
+    bit-exact against the oracle.  n = 70 runs the per-lane I/O (rows need n % 4 == 0), n = 72 the
+    row I/O: of chorus_block_v11 for the pitch-shift kind, of chorus_block_rf1 for the chorus kind (its
+    pitch is set before the first frame, so it stays ring-free; chorus_block_v11<FULL> through phasor
+    wraps and 4,096-frame launches: test_gpu_chorus_modes.test_ring_mode_held_long_run)."""
     frames = 100000
     rng = np.random.default_rng(93)
     p = chorus_params(rng, n)
@@ -516,8 +524,8 @@ def test_chorus_long_run_many_wraps(cuda, kind, n):
 def test_chorus_block_kernel_edges(cuda, kind, n):
     """Row I/O (n % 4 == 0) at a single partial wave (4), a partial last wave (36, 1028), calls of
     252, 4, 8, 260, 1000 and 2048 frames (partial 16-frame chunks), extreme depth / rate corners
-    (the chorus window bound): bit-exact against the oracle; the engine reports the kernel it
-    runs."""
+    (the chorus window bound): bit-exact against the oracle.  kernel_name is the kind's ring kernel;
+    the chorus kind runs chorus_block_rf1 here from frame 0 to the end (Engine.chorus_ring_free)."""
     rng = np.random.default_rng(500 + n)
     p = chorus_params(rng, n)
     p[5, ::3] = 1.0                                        # depth max
