@@ -96,7 +96,7 @@ enum {
                                   OLFX_KIND_VOICE_MOOG + olfx_mix + OLFX_KIND_FXRACK at OLFX_FR_TOPOLOGY 1 give
                                   for the sum in input channel 0.  P = 4 (olfx_create) or 1..8
                                   (olfx_create_synth).  OLFX_SY_* fields and rules below. */
-    OLFX_KIND_SYNTH_SVF = 12   /* the library's own voice as a polyphonic instrument, one launch (synth.hip):
+    OLFX_KIND_SYNTH_SVF = 12,  /* the library's own voice as a polyphonic instrument, one launch (synth.hip):
                                   per instrument, P SynthVoice(OscillatorSoundSource, SvfFilter) -- the default-
                                   constructed SynthVoice, OLFX_KIND_VOICE's -- behind a Polyvoice, into the rack
                                   at the instrument's OLFX_FR_TOPOLOGY: 1 as OLFX_KIND_SYNTH, or 0,
@@ -106,6 +106,20 @@ enum {
                                   OLFX_KIND_VOICE + olfx_mix + OLFX_KIND_FXRACK at that topology give for the sum
                                   in input channel 0 and zeros in channel 1.  P = 4 (olfx_create) or 1..8
                                   (olfx_create_synth_kind).  OLFX_SY_* fields; rules below. */
+    /* 13 stays unassigned: tests/cpp/dump_kinds.cpp (tests/golden/host_kinds.txt), tests/cpp/test_synth_svf_host.cpp
+       and tests/test_synth_svf_host.py pin it as "a kind nobody has" (OLFX_E_KIND) */
+    OLFX_KIND_DRUMKIT = 14     /* the reference's drum machine, one launch (drumkit.hip): per kit, P sample voices
+                                  (SynthVoice(SampleSoundSource<1>(Sample), SvfFilter), OLFX_KIND_VOICE_SAMPLE's, each
+                                  with its own Voice::Config and Sample) behind a VoiceMap (VoiceMap.h:27-82), into
+                                  the rack at the kit's OLFX_FR_TOPOLOGY, 0 or 1 as OLFX_KIND_SYNTH_SVF:
+                                    frame = 0; voicemap.Process(&frame);   for note 0..127 ascending, if a voice sits
+                                                                           there: frame += voice.Process()
+                                    rack on (frame, 0.0f)
+                                  No input; out [2][n_frames][n_kits] -- bit for bit what OLFX_KIND_VOICE_SAMPLE over
+                                  the kit's voices + olfx_mix with one bus per kit listing its mapped voices in
+                                  ascending note order + OLFX_KIND_FXRACK at that topology give for the sum in input
+                                  channel 0 and zeros in channel 1.  P = 4 (olfx_create) or 1..8 (olfx_create_drumkit).
+                                  OLFX_DK_* fields, olfx_drumkit_map; rules below. */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -259,6 +273,51 @@ enum {
 #define OLFX_SY_RACK0     (OLFX_VC_NPARAMS)
 #define OLFX_SY_NPARAMS   (OLFX_VC_NPARAMS + OLFX_FR_NPARAMS)
 
+/* Drum kit (OLFX_KIND_DRUMKIT): eight voice slots of sixteen fields each, then the rack's twelve -- 140 fields
+   whatever the kit's voice count P.
+     field                               meaning                                   default, validation
+     OLFX_DK_VOICE0 + 16 p + OLFX_VC_*   voice slot p's own Voice::Config member   as OLFX_KIND_VOICE_SAMPLE
+                                         (p = 0..7; every pad has its own sample,
+                                         envelopes and filter: SamplePool.h:37-53).
+                                         Slots p >= P are validated and stored like
+                                         the rest and read by nothing, so one
+                                         [140][n] draw fits every P
+     OLFX_DK_RACK0 + OLFX_FR_*           the rack's members                        as OLFX_KIND_SYNTH_SVF: TOPOLOGY
+                                                                                   defaults to 1, accepts 0 or 1
+   olfx_set_params / olfx_set_param_list imply Update() of exactly the voice slots whose fields the call touches (and
+   re-derive the rack when rack fields are touched); olfx_set_member stores a voice member without Update() (refused
+   with OLFX_E_STATE once that slot is Update()d, except the members Process reads, as for the voice kinds);
+   olfx_update(first, count) is Update() of every voice of those kits and of their racks.
+   The map (olfx_drumkit_map) is VoiceMap's two tables per kit, note2voice[128] and channel2voice[16]; it starts
+   empty, is configuration (olfx_reset keeps it, like bank and sample assignments) and takes effect in call order:
+   note events queued earlier were routed by the old map, the next olfx_process sums by the new one.
+   Two departures from VoiceMap, both consequences of the contract above:
+     - a voice that sits at no note is not summed and gets no note events, but it still ticks (its envelopes and
+       its Sample advance), as it does in the composed engines; the reference does not tick it;
+     - a voice may sit at one note only: a call that would leave a voice at two notes is refused (the reference
+       would tick such a voice twice per frame, which olfx_mix_config refuses too).
+   Notes: olfx_note_events NOTE_ON(kit, note, vel) is SynthVoice::NoteOn(note, vel) of the voice at note2voice[note]
+   (with the sample voice's Seek(0) and Play()), NOTE_OFF its NoteOff; a note nobody sits at is ignored
+   (VoiceMap.h:27-43).  GATE_ON, GATE_OFF and SET_FREQUENCY are OLFX_E_ARG: VoiceMap has no such call.
+   olfx_synth_playing / olfx_synth_voices work as for the synth kinds (a voice's Playing() is its last NoteOn's
+   note, 0 after NoteOff; olfx_reset clears it).
+   Controls: olfx_control_event.pad is the MIDI channel (this kind only).  Channel c < 16: the voice at
+   channel2voice[c] gets OLFX_KIND_VOICE_SAMPLE's control mapping on its own fields OLFX_DK_VOICE0 + 16 p + ...,
+   with Update() of that voice only (VoiceMap.h:75-82); an empty entry is ignored.  Channel OLFX_DK_CHANNEL_RACK:
+   the rack's mapping at the kit's topology, as olfx_control has it for OLFX_KIND_SYNTH_SVF's rack.  Other channel
+   values are ignored.  olfx_control_map(OLFX_KIND_DRUMKIT, ...) is OLFX_E_KIND (the mapping needs a channel): use
+   OLFX_KIND_VOICE_SAMPLE's map and add 16 p.
+   Samples: olfx_sample_bank as for OLFX_KIND_VOICE_SAMPLE; olfx_sample_voices takes inst = kit * P + p.
+   Refused (OLFX_E_STATE): olfx_mix_config, olfx_mix (the sum never leaves the kernel). */
+#define OLFX_DK_MAX_VOICES   8
+#define OLFX_DK_VOICE0       0
+#define OLFX_DK_RACK0        (OLFX_DK_MAX_VOICES * OLFX_VC_NPARAMS)
+#define OLFX_DK_NPARAMS      (OLFX_DK_RACK0 + OLFX_FR_NPARAMS)
+#define OLFX_DK_NO_VOICE     0xFFFFFFFFu   /* olfx_drumkit_voice.voice: clear the entries (SetVoice(.., nullptr)) */
+#define OLFX_DK_NO_NOTE      0xFFu         /* olfx_drumkit_voice.note: leave note2voice alone (an extension) */
+#define OLFX_DK_NO_CHANNEL   0xFFu         /* olfx_drumkit_voice.channel: leave channel2voice alone (an extension) */
+#define OLFX_DK_CHANNEL_RACK 16            /* olfx_control_event.pad: the kit's rack */
+
 /* ---- note events (voices) ----
    The ol::synth::Voice calls that change a voice's gate or pitch (Voice.h:33-57), as SynthVoice
    implements them (SynthVoice.h:231-268):
@@ -302,9 +361,25 @@ typedef struct olfx_control_event {
     uint32_t inst;
     uint8_t  control;   /* CC number, corelib/cc_map.h */
     uint8_t  source;    /* OLFX_CTL_MIDI (value 0..127) or OLFX_CTL_HARDWARE (value as given) */
-    uint16_t pad;
+    uint16_t pad;       /* OLFX_KIND_DRUMKIT: the MIDI channel 0..15, or OLFX_DK_CHANNEL_RACK; other kinds ignore it */
     float    value;
 } olfx_control_event;
+
+/* ---- the drum kit's VoiceMap (OLFX_KIND_DRUMKIT) ----
+   Each record is VoiceMap::SetVoice(channel, note, voice) on kit `kit` (VoiceMap.h:45-58): note2voice[note] = voice;
+   channel2voice[channel] = voice.  Whatever sat at that note or channel is displaced (the reference overwrites the
+   entry); voice = OLFX_DK_NO_VOICE clears the entries.  Extensions: note = OLFX_DK_NO_NOTE or channel =
+   OLFX_DK_NO_CHANNEL leaves that table alone.  Records apply in order and the call is judged on the state after its
+   last record: if a voice of a kit would then sit at two notes, or a kit (>= n), voice (>= P), note (128..254) or
+   channel (16..254) is out of range, the call returns OLFX_E_ARG and changes nothing.  (Two voices may swap their
+   notes in one call.) */
+typedef struct olfx_drumkit_voice {
+    uint32_t kit;
+    uint32_t voice;     /* voice slot 0..P-1, or OLFX_DK_NO_VOICE */
+    uint8_t  channel;   /* 0..15, or OLFX_DK_NO_CHANNEL */
+    uint8_t  note;      /* 0..127, or OLFX_DK_NO_NOTE */
+    uint16_t pad;
+} olfx_drumkit_voice;
 
 /* ---- I/O flags ---- */
 enum {
@@ -342,6 +417,10 @@ int olfx_create_synth(int device, uint32_t n_inst, uint32_t voices, float sample
 /* The same for either synth kind: kind is OLFX_KIND_SYNTH or OLFX_KIND_SYNTH_SVF (else OLFX_E_KIND). */
 int olfx_create_synth_kind(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
                            olfx_engine **out);
+/* An OLFX_KIND_DRUMKIT engine of n_kits kits with `voices` (1..8) sample voices each; olfx_create(OLFX_KIND_DRUMKIT,
+   ...) gives 4.  (olfx_create_synth_kind refuses the kind: it is no synth.) */
+int olfx_create_drumkit(int device, uint32_t n_kits, uint32_t voices, float sample_rate, uint32_t block,
+                        olfx_engine **out);
 int olfx_destroy(olfx_engine *e);
 
 /* Zero all state and restore defaults (== destroy + create, without reallocating).  Like
@@ -400,7 +479,8 @@ int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
 int olfx_note_events(olfx_engine *e, const olfx_event *ev, uint32_t n);
 /* The same queue with SET_FREQUENCY (Voice::SetFrequency, SynthVoice.h:264-267) as well. */
 int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n);
-/* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF: Playing() of the `voices` voices of instrument inst, as of the calls made so far. */
+/* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF / OLFX_KIND_DRUMKIT: Playing() of the `voices` voices of instrument (kit) inst,
+   as of the calls made so far. */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);
 
 /* Update() of instances [first, first + count) with their current parameters (SynthVoice.h:66-98,
@@ -462,6 +542,8 @@ typedef struct olfx_sample_voice {
 } olfx_sample_voice;
 int olfx_sample_bank(olfx_engine *e, uint32_t n_samples, const uint64_t *offsets, const float *pcm);
 int olfx_sample_voices(olfx_engine *e, const olfx_sample_voice *recs, uint32_t n);
+/* OLFX_KIND_DRUMKIT: apply n VoiceMap records (above); OLFX_E_STATE on another kind. */
+int olfx_drumkit_map(olfx_engine *e, const olfx_drumkit_voice *recs, uint32_t n);
 
 /* Block until all work queued by this engine is done (engine-scoped, see olfx_reset). */
 int olfx_sync(olfx_engine *e);
@@ -473,7 +555,7 @@ uint32_t olfx_num_instances(const olfx_engine *e);
 int      olfx_kind(const olfx_engine *e);
 uint64_t olfx_frames_processed(const olfx_engine *e);   /* per instance, since create/reset */
 uint32_t olfx_num_buses(const olfx_engine *e);          /* voice buses (olfx_mix_config) */
-uint32_t olfx_synth_voices(const olfx_engine *e);       /* voices per instrument (the synth kinds), else 0 */
+uint32_t olfx_synth_voices(const olfx_engine *e);       /* voices per instrument (the synth kinds, the drum kit), else 0 */
 /* Algorithmic ("compulsory") HBM bytes per instance-frame of the dominant kernel, the figure
    bench.py's roofline uses. */
 double   olfx_algorithmic_bytes_per_frame(const olfx_engine *e);

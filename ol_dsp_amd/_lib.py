@@ -34,6 +34,16 @@ KIND_PLATERACK = 8
 KIND_VOICE_SAMPLE = 10      # 9 is unassigned (olfx.h)
 KIND_SYNTH = 11
 KIND_SYNTH_SVF = 12
+KIND_DRUMKIT = 14           # 13 is unassigned (olfx.h)
+
+DK_MAX_VOICES = 8
+DK_VOICE0 = 0
+DK_RACK0 = 128
+DK_NPARAMS = 140
+DK_NO_VOICE = 0xFFFFFFFF
+DK_NO_NOTE = 0xFF
+DK_NO_CHANNEL = 0xFF
+DK_CHANNEL_RACK = 16
 
 NO_SAMPLE = 0xFFFFFFFF
 SAMPLE_ONESHOT = 0
@@ -107,6 +117,16 @@ class SampleVoice(ctypes.Structure):
     ]
 
 
+class DrumkitVoice(ctypes.Structure):
+    _fields_ = [
+        ("kit", ctypes.c_uint32),
+        ("voice", ctypes.c_uint32),
+        ("channel", ctypes.c_uint8),
+        ("note", ctypes.c_uint8),
+        ("pad", ctypes.c_uint16),
+    ]
+
+
 CTL_MIDI = 0
 CTL_HARDWARE = 1
 IGNORED = 1
@@ -122,6 +142,7 @@ SIGNATURES = {
     "olfx_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_create_synth": (ctypes.c_int, [ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_create_synth_kind": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
+    "olfx_create_drumkit": (ctypes.c_int, [ctypes.c_int, _U32, _U32, _F, _U32, ctypes.POINTER(_P)]),
     "olfx_destroy": (ctypes.c_int, [_P]),
     "olfx_reset": (ctypes.c_int, [_P]),
     "olfx_set_params": (ctypes.c_int, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(_F)]),
@@ -157,6 +178,7 @@ SIGNATURES = {
     "olfx_synth_playing": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint8)]),
     "olfx_sample_bank": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_F)]),
     "olfx_sample_voices": (ctypes.c_int, [_P, ctypes.POINTER(SampleVoice), _U32]),
+    "olfx_drumkit_map": (ctypes.c_int, [_P, ctypes.POINTER(DrumkitVoice), _U32]),
     # include/olfx_sample.h: per-instance, per-sample operators (one block of latency)
     "olfx_sample_pool_config": (ctypes.c_int, [ctypes.c_int, _U32]),
     "olfx_sample_pool_config_depth": (ctypes.c_int, [ctypes.c_int, _U32, _U32]),

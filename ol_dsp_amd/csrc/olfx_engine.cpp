@@ -138,6 +138,9 @@ struct olfx_engine {
     uint32_t *sm_asg = nullptr;
     float *sm_bank = nullptr;
     uint64_t sm_bank_bytes = 0;
+    // the drum kit: each kit's sum order ([n], DKC_ORDER); its voices' planes are vc_state, vc_coef and sm_asg
+    // over the voice slots
+    uint32_t *dk_order = nullptr;
     // voice buses (olfx_mix_config): [n_buses + 1] offsets, then the voice lists
     uint32_t *mix_dev = nullptr;
     uint32_t mix_quad = 0;                  // contiguous buses on multiples of 4 voices (voice_mix_v4)
@@ -187,7 +190,7 @@ size_t carve(olfx_engine *e, char *base) {
     };
     const int kind = e->kind;
     const size_t n = e->n, nd = e->n_dt;
-    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK || is_synth_kind(kind)) {
+    if (kind == OLFX_KIND_FXRACK || kind == OLFX_KIND_PLATERACK || is_synth_kind(kind) || kind == OLFX_KIND_DRUMKIT) {
         take(e->fr_ring, (size_t)kFrMaxDelay * 2 * n * 4);
         take(e->fr_state, (size_t)FRS_N * n * 4);
         take(e->fr_coef, (size_t)FRC_N * n * 4);
@@ -219,6 +222,14 @@ size_t carve(olfx_engine *e, char *base) {
         take(e->vc_state, (size_t)voice_state_slots(kind) * e->hs.n_ev() * 4);
         take(e->vc_coef, (size_t)VCC_N * n * 4);
     }
+    if (kind == OLFX_KIND_DRUMKIT) {
+        // every voice slot's state, coefficients and Sample (voices x n rounded up to 64); the kits' sum orders
+        const size_t slots = e->hs.n_ev();
+        take(e->vc_state, (size_t)VCS_N * slots * 4);
+        take(e->vc_coef, (size_t)VCC_N * slots * 4);
+        take(e->sm_asg, (size_t)SMC_N * slots * 4);
+        take(e->dk_order, (size_t)DKC_N * n * 4);
+    }
     return off;
 }
 
@@ -228,25 +239,30 @@ size_t carve(olfx_engine *e, char *base) {
 // ---------------------------------------------------------------------------------------------
 
 // The destination arrays (field-major, CoefScatterArgs) of a coefficient record's segments: each part
-// of the kind goes to the array its row names (host::Dst); returns the record's words.
-uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a) {
+// of the kind goes to the array its row names (host::Dst); returns the record's words.  voice_slots: the
+// record of a kit kind's voice slot instead (KindDesc::vparts).
+uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a, bool voice_slots = false) {
+    const host::KindDesc &kd = *e->hs.kd;
+    // a kit's voice arrays are indexed by voice slot (p * npad + kit)
+    const uint32_t nv = kd.voice_slots ? e->hs.n_ev() : e->n;
     const struct { void *p; uint32_t stride; } to[host::TO_COUNT] = {
         /* TO_DT */ {e->dt_coef, e->n_dt},       // padding plate instances keep their zeroed coefficients
         /* TO_CH */ {e->ch_coef, e->n},
         /* TO_PS */ {e->ps_coef, e->n},
-        /* TO_VC */ {e->vc_coef, e->n},
+        /* TO_VC */ {e->vc_coef, nv},
         /* TO_FR */ {e->fr_coef, e->n},
-        /* TO_SM */ {e->sm_asg, e->n},
+        /* TO_SM */ {e->sm_asg, nv},
+        /* TO_ORD */ {e->dk_order, e->n},
     };
-    const host::KindDesc &kd = *e->hs.kd;
-    const host::Segments sg = host::coef_segments(e->kind);
+    const host::Segments sg = voice_slots ? host::voice_segments(e->kind) : host::coef_segments(e->kind);
+    const host::Part *parts = voice_slots ? kd.vparts : kd.parts;
     a->nseg = sg.nseg;
     for (uint32_t k = 0; k < sg.nseg; ++k) {
-        a->dst[k] = (uint32_t *)to[kd.parts[k].dst].p;
+        a->dst[k] = (uint32_t *)to[parts[k].dst].p;
         a->words[k] = sg.words[k];
-        a->stride[k] = to[kd.parts[k].dst].stride;
+        a->stride[k] = to[parts[k].dst].stride;
     }
-    return kd.words;
+    return voice_slots ? kd.vwords : kd.words;
 }
 
 // Record one marker after the pending slots' kernels (on their stream) and make it their guard.
@@ -330,8 +346,8 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     *used_slot = nullptr;
     host::Shadow &hs = e->hs;
     const bool evs = host::takes_note_events(e->kind) && !hs.events.empty();
-    const size_t m = hs.dirty_list.size();
-    if (!m && !evs) return OLFX_OK;
+    const size_t m = hs.dirty_list.size(), m2 = hs.vdirty_list.size();    // (m2: a kit kind's voice slots)
+    if (!m && !m2 && !evs) return OLFX_OK;
     using clk = std::chrono::steady_clock;
     auto t_prev = clk::now();
     auto lap = [&](int k) {
@@ -397,6 +413,15 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
         ca.W = W;
         const hipError_t r = launch_coef_scatter(ca, s);
         if (r != hipSuccess) return e->hip_fail(r, "coefficient scatter launch");
+    }
+    if (m2) {
+        CoefScatterArgs cv{};
+        cv.W = coef_segments(e, &cv, true);
+        cv.inst = dev + pl.o_inst2;
+        cv.val = dev + pl.o_val2;
+        cv.m = (uint32_t)m2;
+        const hipError_t r = launch_coef_scatter(cv, s);
+        if (r != hipSuccess) return e->hip_fail(r, "voice-slot coefficient scatter launch");
     }
     if (evs) {
         va->ev = reinterpret_cast<const uint2 *>(dev + pl.o_ev);
@@ -619,6 +644,30 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_synth(a, s);
         break;
     }
+    case OLFX_KIND_DRUMKIT: {
+        // one fused launch: the sample-voice waves feed the delay waves and the filter wave through LDS
+        DrumkitArgs a{};
+        a.ring = e->fr_ring;
+        a.fr_state = e->fr_state;
+        a.fr_coef = e->fr_coef;
+        a.vc_state = e->vc_state;
+        a.vc_coef = e->vc_coef;
+        a.smp = e->sm_asg;
+        a.order = e->dk_order;
+        a.bank = e->sm_bank;
+        a.bank_bytes = (uint32_t)e->sm_bank_bytes;
+        a.out = dout;
+        a.plane = plane;
+        a.n = e->n;
+        a.n_frames = n_frames;
+        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
+        a.voices = e->hs.voices;
+        a.npad = e->hs.npad;
+        a.ev = ev.ev;
+        a.ev_more = ev.ev_more;
+        r = launch_drumkit(a, s);
+        break;
+    }
     case OLFX_KIND_CHAIN: {
         // one fused launch: chorus and pitch-shift waves feed the reverb wave through LDS
         ChainArgs a{};
@@ -750,6 +799,17 @@ int olfx_create_synth_kind(int kind, int device, uint32_t n_inst, uint32_t voice
     return create_engine(kind, device, n_inst, voices, sample_rate, block, out);
 }
 
+int olfx_create_drumkit(int device, uint32_t n_kits, uint32_t voices, float sample_rate, uint32_t block,
+                        olfx_engine **out) {
+    if (!out) return OLFX_E_ARG;
+    *out = nullptr;
+    if (voices < 1 || voices > kDkMaxVoices) {
+        set_global_error("olfx_create_drumkit: %u voices per kit (1..%u)", voices, kDkMaxVoices);
+        return OLFX_E_ARG;
+    }
+    return create_engine(OLFX_KIND_DRUMKIT, device, n_kits, voices, sample_rate, block, out);
+}
+
 static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices, float sample_rate, uint32_t block,
                          olfx_engine **out) {
     if (!out) return OLFX_E_ARG;
@@ -758,8 +818,8 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
         set_global_error("olfx_create: unknown kind %d", kind);
         return OLFX_E_KIND;
     }
-    // (the synth's voice slots, voices x n rounded up to 64, are indexed in 32 bits)
-    const bool too_many = is_synth_kind(kind) && ((uint64_t)n_inst + 63u) / 64u * 64u * voices > 0x7FFFFFFFull;
+    // (the synths' and the drum kit's voice slots, voices x n rounded up to 64, are indexed in 32 bits)
+    const bool too_many = host::kind_desc(kind).instances == host::KindDesc::INSTRUMENTS && ((uint64_t)n_inst + 63u) / 64u * 64u * voices > 0x7FFFFFFFull;
     if (n_inst == 0 || too_many || !(sample_rate > 1000.f && sample_rate <= 384000.f) || block == 0 || (block & 3u)) {
         set_global_error("olfx_create: bad argument (n_inst=%u sr=%g block=%u)", n_inst, sample_rate, block);
         return OLFX_E_ARG;
@@ -1110,6 +1170,10 @@ int olfx_sample_voices(olfx_engine *e, const olfx_sample_voice *recs, uint32_t n
     return e ? e->report(e->hs.sample_voices(recs, n)) : OLFX_E_ARG;
 }
 
+int olfx_drumkit_map(olfx_engine *e, const olfx_drumkit_voice *recs, uint32_t n) {
+    return e ? e->report(e->hs.drumkit_map(recs, n)) : OLFX_E_ARG;
+}
+
 int olfx_sync(olfx_engine *e) {
     if (!e) return OLFX_E_ARG;
     HIPCHK(e, hipSetDevice(e->device));
@@ -1125,10 +1189,11 @@ uint32_t olfx_num_buses(const olfx_engine *e) { return e ? e->n_buses : 0; }
 uint32_t olfx_synth_voices(const olfx_engine *e) { return e ? e->hs.voices : 0; }
 
 double olfx_algorithmic_bytes_per_frame(const olfx_engine *e) {
-    return e ? host::algorithmic_bytes_per_frame(e->kind) : 0.0;
+    // (a drum kit reads 4 B of sample per voice and frame on top of its row's figure)
+    return e ? host::algorithmic_bytes_per_frame(e->kind) + (e->hs.kit() ? 4.0 * e->hs.voices : 0.0) : 0.0;
 }
 double olfx_algorithmic_read_bytes_per_frame(const olfx_engine *e) {
-    return e ? host::algorithmic_read_bytes_per_frame(e->kind) : 0.0;
+    return e ? host::algorithmic_read_bytes_per_frame(e->kind) + (e->hs.kit() ? 4.0 * e->hs.voices : 0.0) : 0.0;
 }
 
 const char *olfx_kernel_name(const olfx_engine *e) {

@@ -360,9 +360,12 @@ constexpr Component kComponents[CP_COUNT] = {
     // the voice's Sample assignment: no parameters, its words come from olfx_sample_voices
     /* CP_SAMPLE */ {0, SMC_N, nullptr,
                      [](const float *, const Shadow &s, uint32_t i, uint32_t *w) { s.sample_record(i, w); }},
+    // a kit's sum order: no parameters, its word comes from olfx_drumkit_map
+    /* CP_ORDER  */ {0, DKC_N, nullptr,
+                     [](const float *, const Shadow &s, uint32_t i, uint32_t *w) { w[DKC_ORDER] = s.order_word(i); }},
 };
 
-constexpr size_t kKinds = OLFX_KIND_SYNTH_SVF + 1;     // kind numbers 0 .. the last; 0 and 9 are no kinds
+constexpr size_t kKinds = OLFX_KIND_DRUMKIT + 1;       // kind numbers 0 .. the last; 0, 9 and 13 are no kinds
 
 constexpr std::array<KindDesc, kKinds> kKindTable = [] {
     std::array<KindDesc, kKinds> t{};
@@ -455,6 +458,21 @@ constexpr std::array<KindDesc, kKinds> kKindTable = [] {
     k->set[k->nset++] = {OLFX_SY_RACK0 + OLFX_FR_TOPOLOGY, 1.f};
     // the Svf synth runs the rack proper (0) as well; the components alone (2..4) have no voices in front
     k->topologies = 0x3; k->topology_msg = "svf synth rack topology must be 0 or 1";
+    // the reference's drum machine: the rack and the sum order are the kit's record; eight slots of sample-voice
+    // fields in front of the rack's, each slot a record of its own (voice coefficients, then its Sample)
+    k = &row(OLFX_KIND_DRUMKIT, {{CP_RACK, OLFX_DK_RACK0, TO_FR}, {CP_ORDER, 0, TO_ORD}}, "drumkit_block_v1",
+             32.0 - 8.0,                  // as the synths; the engine adds 4 B of sample read per voice of the kit
+             16.0 - 8.0);
+    k->in_ch = 0; k->instances = KindDesc::INSTRUMENTS;
+    k->voice_slots = kDkMaxVoices;
+    k->vparts[k->nvparts++] = {CP_VOICE, OLFX_DK_VOICE0, TO_VC};
+    k->vparts[k->nvparts++] = {CP_SAMPLE, OLFX_DK_VOICE0, TO_SM};
+    k->vwords = kComponents[CP_VOICE].words + kComponents[CP_SAMPLE].words;
+    k->n_params += kDkMaxVoices * OLFX_VC_NPARAMS;
+    k->voice0 = OLFX_DK_VOICE0; k->voice_end = OLFX_DK_RACK0;
+    k->has_sample = true;
+    k->set[k->nset++] = {OLFX_DK_RACK0 + OLFX_FR_TOPOLOGY, 1.f};
+    k->topologies = 0x3; k->topology_msg = "drum kit rack topology must be 0 or 1";
     return t;
 }();
 
@@ -480,6 +498,10 @@ void default_params(int kind, float *p) {
     const KindDesc &k = kind_desc(kind);
     for (uint32_t j = 0; j < k.nparts; ++j)
         if (const auto defaults = kComponents[k.parts[j].comp].defaults) defaults(p + k.parts[j].field0);
+    for (uint32_t slot = 0; slot < k.voice_slots; ++slot)
+        for (uint32_t j = 0; j < k.nvparts; ++j)
+            if (const auto defaults = kComponents[k.vparts[j].comp].defaults)
+                defaults(p + k.vparts[j].field0 + slot * OLFX_VC_NPARAMS);
     for (uint32_t j = 0; j < k.nset; ++j) p[k.set[j].field] = k.set[j].value;
 }
 
@@ -487,6 +509,13 @@ Segments coef_segments(int kind) {
     const KindDesc &k = kind_desc(kind);
     Segments sg{k.nparts, {0, 0, 0}};
     for (uint32_t j = 0; j < k.nparts; ++j) sg.words[j] = kComponents[k.parts[j].comp].words;
+    return sg;
+}
+
+Segments voice_segments(int kind) {
+    const KindDesc &k = kind_desc(kind);
+    Segments sg{k.nvparts, {0, 0, 0}};
+    for (uint32_t j = 0; j < k.nvparts; ++j) sg.words[j] = kComponents[k.vparts[j].comp].words;
     return sg;
 }
 
@@ -512,6 +541,9 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
         case CP_SAMPLE: bytes += (uint64_t)SMC_N * 4 * n; break;
         default: break;
         }
+    // a kit's voices: each its own state, coefficients and Sample words
+    for (uint32_t j = 0; j < k.nvparts; ++j)
+        bytes += voices * (kComponents[k.vparts[j].comp].words + (k.vparts[j].comp == CP_VOICE ? (uint64_t)VCS_N : 0u)) * 4 * n;
     return bytes;
 }
 
@@ -523,6 +555,26 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
         c.derive(p + kd->parts[j].field0, *this, i, w);
         w += c.words;
     }
+}
+
+void Shadow::derive_voice_record(uint32_t hv, uint32_t *w) const {
+    const uint32_t p = hv / n, i = hv % n;
+    float v[OLFX_VC_NPARAMS];
+    for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) v[f] = params[(size_t)(kd->voice0 + p * OLFX_VC_NPARAMS + f) * n + i];
+    derive_voice(v, configured[hv] != 0, kd->moog, sr, w);
+    sample_record(i * voices + p, w + VCC_N);
+}
+
+// VoiceMap::Process (VoiceMap.h:64-73) visits the notes in ascending order; a valid map holds each voice once
+uint32_t Shadow::order_word(uint32_t kit_) const {
+    uint32_t word = kDkOrderEmpty, k = 0;
+    for (uint32_t note = 0; note < 128 && k < 8; ++note) {
+        const uint8_t v = note2voice[(size_t)note * n + kit_];
+        if (v == kNoVoice) continue;
+        word = (word & ~(0xFu << (4 * k))) | (uint32_t)v << (4 * k);
+        ++k;
+    }
+    return word;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -542,7 +594,10 @@ void Shadow::reset() {
     default_params(kind, d);
     for (uint32_t f = 0; f < n_params; ++f)
         std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
-    configured.assign(n, 0);
+    configured.assign(kit() ? (size_t)voices * n : n, 0);
+    vdirty_list.clear();
+    vdirty_mark.assign(kit() ? (size_t)voices * n : 0u, 0);
+    for (uint32_t hv = 0; hv < vdirty_mark.size(); ++hv) mark_vdirty(hv);
     n_components = 0;
     pre_changed = true;
     events.clear();
@@ -562,6 +617,30 @@ void Shadow::mark_dirty(uint32_t first, uint32_t count) {
             dirty_mark[k] = 1;
             dirty_list.push_back(k);
         }
+}
+
+void Shadow::mark_vdirty(uint32_t hv) {
+    if (!vdirty_mark[hv]) {
+        vdirty_mark[hv] = 1;
+        vdirty_list.push_back(hv);
+    }
+}
+
+void Shadow::touched(uint32_t inst, uint32_t field0, uint32_t n_fields) {
+    if (!kit()) {
+        if (touches_voice(field0, n_fields)) configured[inst] = 1;
+        mark_dirty(inst, 1);
+        return;
+    }
+    // the voice slots whose sixteen fields the range meets (slots past the kit's voices are read by nothing)
+    for (uint32_t p = 0; p < voices; ++p) {
+        const uint32_t lo = kd->voice0 + p * OLFX_VC_NPARAMS;
+        if (n_fields && field0 < lo + OLFX_VC_NPARAMS && field0 + n_fields > lo) {
+            configured[(size_t)p * n + inst] = 1;
+            mark_vdirty(p * n + inst);
+        }
+    }
+    if (field0 + n_fields > kd->voice_end) mark_dirty(inst, 1);       // the rack's
 }
 
 // A parameter value the reference's setter gives a meaning to (nullptr) or why not.
@@ -596,9 +675,7 @@ int Shadow::set_range(uint32_t first, uint32_t count, uint32_t field0, uint32_t 
                 return fail(OLFX_E_ARG, "olfx_set_params: %s", why);
     for (uint32_t f = 0; f < n_fields; ++f)
         for (uint32_t k = 0; k < count; ++k) store_param(field0 + f, first + k, values[(size_t)f * count + k]);
-    if (touches_voice(field0, n_fields))
-        for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
-    mark_dirty(first, count);
+    for (uint32_t k = 0; k < count; ++k) touched(first + k, field0, n_fields);
     return OLFX_OK;
 }
 
@@ -611,8 +688,7 @@ int Shadow::set_list(uint32_t field, const uint32_t *inst, const float *values, 
     }
     for (uint32_t k = 0; k < count; ++k) {
         store_param(field, inst[k], values[k]);
-        if (touches_voice(field, 1)) configured[inst[k]] = 1;
-        mark_dirty(inst[k], 1);
+        touched(inst[k], field, 1);
     }
     return OLFX_OK;
 }
@@ -626,8 +702,20 @@ int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
     // sample (SynthVoice.h:42-52): writing them takes effect at once, Update()d or not.  Re-deriving
     // at the next block changes nothing else, since every other member still holds the value the
     // last Update() saw (they change only through olfx_set_params, i.e. with an Update()).
-    const bool process_reads = field == OLFX_VC_FILTER_CUTOFF || field == OLFX_VC_FILTER_ENV_AMOUNT ||
-                               field == OLFX_VC_AMP_ENV_AMOUNT;
+    const uint32_t vf = (field - kd->voice0) % OLFX_VC_NPARAMS, slot = (field - kd->voice0) / OLFX_VC_NPARAMS;
+    const bool process_reads = vf == OLFX_VC_FILTER_CUTOFF || vf == OLFX_VC_FILTER_ENV_AMOUNT ||
+                               vf == OLFX_VC_AMP_ENV_AMOUNT;
+    if (kit()) {
+        // the member of voice slot `slot` alone; a slot past the kit's voices is stored and read by nothing
+        if (slot < voices) {
+            if (configured[(size_t)slot * n + inst] && !process_reads)
+                return fail(OLFX_E_STATE, "olfx_set_member: voice %u of kit %u is already Update()d (use olfx_set_params)",
+                            slot, inst);
+            mark_vdirty(slot * n + inst);
+        }
+        store_param(field, inst, value);
+        return OLFX_OK;
+    }
     // the other members feed the components only through Update() (SynthVoice.h:66-98); written
     // after the first Update() they would take effect at the next block as if Update() had run,
     // which SynthVoice does not do: refused instead of silently diverging
@@ -640,8 +728,15 @@ int Shadow::set_member(uint32_t inst, uint32_t field, float value) {
 
 int Shadow::update(uint32_t first, uint32_t count) {
     if ((uint64_t)first + count > n) return fail(OLFX_E_ARG, "olfx_update: range out of bounds");
-    if (kd->takes_note_events())
+    if (kit()) {                            // every voice of those kits, and their racks
+        for (uint32_t p = 0; p < voices; ++p)
+            for (uint32_t k = 0; k < count; ++k) {
+                configured[(size_t)p * n + first + k] = 1;
+                mark_vdirty(p * n + first + k);
+            }
+    } else if (kd->takes_note_events()) {
         for (uint32_t k = 0; k < count; ++k) configured[first + k] = 1;
+    }
     mark_dirty(first, count);
     return OLFX_OK;
 }
@@ -676,14 +771,17 @@ void Shadow::bank_commit(BankPlan &&plan) {
         if (a.sample != OLFX_NO_SAMPLE && a.sample >= bank.len.size()) a = SampleAsg{OLFX_NO_SAMPLE, 0, 0, 0, a.gen};
         ++a.gen;                            // a fresh Sample over the new data
     }
-    mark_dirty(0, n);
+    if (kit())
+        for (uint32_t hv = 0; hv < voices * n; ++hv) mark_vdirty(hv);
+    else
+        mark_dirty(0, n);
 }
 
 int Shadow::sample_voices(const olfx_sample_voice *recs, uint32_t count) {
     if (!kd->has_sample) return fail(OLFX_E_STATE, "olfx_sample_voices: not a sample-voice engine");
     if (count && !recs) return fail(OLFX_E_ARG, "olfx_sample_voices: null records");
     for (uint32_t k = 0; k < count; ++k) {
-        if (recs[k].inst >= n) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: voice out of range", k);
+        if (recs[k].inst >= n_voices()) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: voice out of range", k);
         if (recs[k].sample != OLFX_NO_SAMPLE && recs[k].sample >= bank.len.size())
             return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: sample %u of %zu", k, recs[k].sample, bank.len.size());
         if (recs[k].play_mode > OLFX_SAMPLE_LOOP) return fail(OLFX_E_ARG, "olfx_sample_voices: record %u: bad play mode", k);
@@ -695,7 +793,8 @@ int Shadow::sample_voices(const olfx_sample_voice *recs, uint32_t count) {
         a.mode = recs[k].play_mode;
         a.loop_start = recs[k].loop_start;
         a.loop_end = recs[k].loop_end;
-        mark_dirty(recs[k].inst, 1);
+        if (kit()) mark_vdirty((recs[k].inst % voices) * n + recs[k].inst / voices);   // inst = kit * voices + p
+        else mark_dirty(recs[k].inst, 1);
     }
     return OLFX_OK;
 }
@@ -870,6 +969,22 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
+        if (kit() && ev[k].pad != OLFX_DK_CHANNEL_RACK) {
+            // VoiceMap::UpdateMidiControl (VoiceMap.h:75-82): the voice at channel2voice[channel], alone
+            if (ev[k].source != OLFX_CTL_MIDI && ev[k].source != OLFX_CTL_HARDWARE) return fail(OLFX_E_ARG, "olfx_control: event %u", k);
+            const uint8_t p = ev[k].pad < 16 ? chan2voice[(size_t)ev[k].pad * n + ev[k].inst] : kNoVoice;
+            if (p == kNoVoice) continue;                  // an empty entry, or no channel at all
+            uint32_t f = 0;
+            float v = 0.f;
+            if (voice_cc(ev[k].control, CcValue{ev[k].source == OLFX_CTL_MIDI, ev[k].value, &f, &v}) != OLFX_OK) continue;
+            if (f == OLFX_FIELD_UPDATE_ONLY) {
+                configured[(size_t)p * n + ev[k].inst] = 1;
+                mark_vdirty(p * n + ev[k].inst);
+            } else if (const int r2 = set_range(ev[k].inst, 1, kd->voice0 + p * OLFX_VC_NPARAMS + f, 1, &v)) {
+                return r2;
+            }
+            continue;
+        }
         const uint32_t topology = kd->topo_field == kNoField ? 0u : (uint32_t)params[(size_t)kd->topo_field * n + ev[k].inst];
         uint32_t fields[2];
         float vals[2];
@@ -877,7 +992,7 @@ int Shadow::control(const olfx_control_event *ev, uint32_t count) {
         if (hits < 0) return fail(hits, "olfx_control: event %u", k);
         for (int h = 0; h < hits; ++h) {
             if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {    // Update() with unchanged members (the voices': now configured)
-                if (kd->takes_note_events()) configured[ev[k].inst] = 1;
+                if (kd->takes_note_events() && !kit()) configured[ev[k].inst] = 1;
                 mark_dirty(ev[k].inst, 1);
             } else if (const int r2 = set_range(ev[k].inst, 1, fields[h], 1, &vals[h])) {
                 return r2;
@@ -893,9 +1008,12 @@ int Shadow::note_events(const olfx_event *ev, uint32_t count) {
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_GATE_OFF)
             return fail(OLFX_E_ARG, "olfx_note_events: bad event %u", k);
+        if (kit() && ev[k].type > OLFX_EV_NOTE_ON)
+            return fail(OLFX_E_ARG, "olfx_note_events: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
     }
     for (uint32_t k = 0; k < count; ++k) {
-        if (instruments()) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        if (kit()) route_kit(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        else if (instruments()) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         else events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
     }
     return OLFX_OK;
@@ -908,6 +1026,12 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
         if (ev[k].inst >= n || ev[k].note > 127 || ev[k].type > OLFX_EV_SET_FREQUENCY ||
             (ev[k].type == OLFX_EV_SET_FREQUENCY && !std::isfinite(ev[k].value)))
             return fail(OLFX_E_ARG, "olfx_voice_events: bad event %u", k);
+        if (kit() && ev[k].type > OLFX_EV_NOTE_ON)
+            return fail(OLFX_E_ARG, "olfx_voice_events: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
+    }
+    if (kit()) {
+        for (uint32_t k = 0; k < count; ++k) route_kit(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        return OLFX_OK;
     }
     if (instruments()) {
         for (uint32_t k = 0; k < count; ++k) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
@@ -950,6 +1074,61 @@ void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velo
         break;
     default: break;                                       // SetFrequency: a nop (Polyvoice.h:77)
     }
+}
+
+// ol::synth::VoiceMap's NoteOn / NoteOff on kit `inst` (VoiceMap.h:27-43): the voice at note2voice[note] gets the
+// call, a note nobody sits at is ignored.  Playing() as in route_synth.
+void Shadow::route_kit(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
+    const uint8_t p = note2voice[(size_t)note * n + inst];
+    if (p == kNoVoice) return;
+    events.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
+    playing[(size_t)p * n + inst] = type == OLFX_EV_NOTE_ON ? note : 0;
+}
+
+int Shadow::drumkit_map(const olfx_drumkit_voice *recs, uint32_t count) {
+    if (!kit()) return fail(OLFX_E_STATE, "olfx_drumkit_map: not a drum kit engine");
+    if (count && !recs) return fail(OLFX_E_ARG, "olfx_drumkit_map: null records");
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_drumkit_voice &r = recs[k];
+        if (r.kit >= n) return fail(OLFX_E_ARG, "olfx_drumkit_map: record %u: kit out of range", k);
+        if (r.voice != OLFX_DK_NO_VOICE && r.voice >= voices)
+            return fail(OLFX_E_ARG, "olfx_drumkit_map: record %u: voice %u of %u", k, r.voice, voices);
+        if (r.note != OLFX_DK_NO_NOTE && r.note > 127) return fail(OLFX_E_ARG, "olfx_drumkit_map: record %u: note out of range", k);
+        if (r.channel != OLFX_DK_NO_CHANNEL && r.channel > 15)
+            return fail(OLFX_E_ARG, "olfx_drumkit_map: record %u: channel out of range", k);
+    }
+    // apply in order, remembering what each write replaced; judge the result; undo on refusal
+    struct Undo { uint8_t *at; uint8_t was; };
+    std::vector<Undo> undo;
+    std::vector<uint32_t> kits;
+    auto put = [&](uint8_t &slot, uint8_t v) {
+        undo.push_back(Undo{&slot, slot});
+        slot = v;
+    };
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_drumkit_voice &r = recs[k];
+        const uint8_t v = r.voice == OLFX_DK_NO_VOICE ? kNoVoice : (uint8_t)r.voice;
+        if (r.note != OLFX_DK_NO_NOTE) put(note2voice[(size_t)r.note * n + r.kit], v);
+        if (r.channel != OLFX_DK_NO_CHANNEL) put(chan2voice[(size_t)r.channel * n + r.kit], v);
+        kits.push_back(r.kit);
+    }
+    std::sort(kits.begin(), kits.end());
+    kits.erase(std::unique(kits.begin(), kits.end()), kits.end());
+    for (const uint32_t i : kits) {
+        uint32_t seen = 0;
+        for (uint32_t note = 0; note < 128; ++note) {
+            const uint8_t v = note2voice[(size_t)note * n + i];
+            if (v == kNoVoice) continue;
+            if (seen >> v & 1u) {
+                // the reference would tick the voice twice per frame (as a voice listed twice, olfx_mix_config)
+                for (size_t u = undo.size(); u-- > 0;) *undo[u].at = undo[u].was;
+                return fail(OLFX_E_ARG, "olfx_drumkit_map: voice %u of kit %u would sit at two notes", (unsigned)v, i);
+            }
+            seen |= 1u << v;
+        }
+    }
+    for (const uint32_t i : kits) mark_dirty(i, 1);       // the sum order
+    return OLFX_OK;
 }
 
 int Shadow::synth_playing(uint32_t inst, uint8_t *out) {
@@ -1049,12 +1228,18 @@ void Shadow::write_events(uint32_t *fix) {
         }
 }
 
-PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev) {
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev, size_t m2, uint32_t W2) {
     PacketPlan pl;
     pl.dense = m == n;                                   // every instance: no instance list
     pl.o_inst = 0;
     pl.o_val = pl.o_inst + (pl.dense ? 0 : up4(m));
     pl.o_ev = up4(pl.o_val + (size_t)W * m);
+    if (m2) {                                            // a kit kind's voice-slot records
+        pl.m2 = m2;
+        pl.o_inst2 = pl.o_ev;
+        pl.o_val2 = pl.o_inst2 + up4(m2);
+        pl.o_ev = up4(pl.o_val2 + (size_t)W2 * m2);
+    }
     pl.words = pl.o_ev + (evs ? 2 * ((size_t)(((n_ev ? n_ev : n) + 63u) / 64u) * kVevCap + n_more) : 0);
     return pl;
 }
@@ -1062,7 +1247,10 @@ PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_mo
 size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev) {
     const size_t n = n_inst, W = coef_segments(kind).total(), nv = n_ev ? n_ev : n_inst;
     const size_t ev = takes_note_events(kind) ? 2 * ((nv + 63) / 64 * kVevCap + nv) : 0;
-    return n + W * n + ev + 16;
+    // a kit kind: every voice slot's list entry and record as well (n_ev = voices x n rounded up to 64)
+    const KindDesc &kd = kind_desc(kind);
+    const size_t nslots = kd.voice_slots ? nv / ((n + 63) / 64 * 64) * n : 0;
+    return n + W * n + nslots * (1 + kd.vwords) + ev + (nslots ? 24 : 16);
 }
 
 // the words psv depends on (chorus_stage_rf.h): the pitch phasor's increment and the window
@@ -1100,6 +1288,19 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     }
     for (const uint32_t i : dirty_list) dirty_mark[i] = 0;
     dirty_list.clear();
+    // a kit kind's voice slots: listed by device slot p * npad + kit
+    if (pl.m2) {
+        const uint32_t W2 = kd->vwords;
+        h_words.resize(W2);
+        for (size_t r = 0; r < pl.m2; ++r) {
+            const uint32_t hv = vdirty_list[r];
+            buf[pl.o_inst2 + r] = hv / n * npad + hv % n;
+            derive_voice_record(hv, h_words.data());
+            for (uint32_t w = 0; w < W2; ++w) buf[pl.o_val2 + (size_t)w * pl.m2 + r] = h_words[w];
+            vdirty_mark[hv] = 0;
+        }
+        vdirty_list.clear();
+    }
     if (pitch_changed && rf.changed()) rf_materialise = true;
 }
 
@@ -1114,7 +1315,8 @@ extern "C" int olfx_control_map(int kind, uint8_t control, int source, float val
     using namespace olfx::host;
     if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
     const KindDesc &kd = kind_desc(kind);
-    // the synths' controls can hit two fields: olfx_synth_control_map / olfx_synth_control_map_at
+    // the synths' controls can hit two fields: olfx_synth_control_map / olfx_synth_control_map_at; the drum
+    // kit's need a channel
     if (kd.instances == KindDesc::INSTRUMENTS) return OLFX_E_KIND;
     uint32_t f[2];
     float v[2];
@@ -1137,7 +1339,8 @@ extern "C" int olfx_synth_control_map_at(int kind, uint32_t topology, uint8_t co
                                          uint32_t field[2], float param_value[2]) {
     using namespace olfx::host;
     const KindDesc &kd = kind_desc(kind);
-    if (kd.instances != KindDesc::INSTRUMENTS) return OLFX_E_KIND;
+    // (a drum kit routes by channel: the voice kind's map for a voice, the rack kind's for the rack)
+    if (kd.instances != KindDesc::INSTRUMENTS || kd.voice_slots) return OLFX_E_KIND;
     if (!field || !param_value || (source != OLFX_CTL_MIDI && source != OLFX_CTL_HARDWARE)) return OLFX_E_ARG;
     if (topology > 4u || !(kd.topologies >> topology & 1)) return OLFX_E_ARG;
     return route_control(kd, topology, control, source, value, field, param_value);

@@ -17,9 +17,9 @@ namespace host __attribute__((visibility("hidden"))) {
 
 // ---- components and kinds (the table is in olfx_host.cpp) ----
 // A component is the unit that has parameters, defaults, a setter restatement and a coefficient block.
-enum Comp : uint8_t { CP_PLATE, CP_CHORUS, CP_PITCH, CP_VOICE, CP_RACK, CP_SAMPLE, CP_COUNT };
+enum Comp : uint8_t { CP_PLATE, CP_CHORUS, CP_PITCH, CP_VOICE, CP_RACK, CP_SAMPLE, CP_ORDER, CP_COUNT };
 // The engine's coefficient arrays (olfx_engine.cpp gives each its pointer and stride).
-enum Dst : uint8_t { TO_DT, TO_CH, TO_PS, TO_VC, TO_FR, TO_SM, TO_COUNT };
+enum Dst : uint8_t { TO_DT, TO_CH, TO_PS, TO_VC, TO_FR, TO_SM, TO_ORD, TO_COUNT };
 // A component of a kind: where its parameters start in the kind's fields, where its coefficients go.
 struct Part { Comp comp; uint8_t field0; Dst dst; };
 constexpr uint32_t kNoField = 0xFFFFFFFFu;
@@ -30,6 +30,11 @@ struct KindDesc {
     // rack part's topology field (kNoField: no such part); a voice part's fields; whether there is a Sample
     uint32_t n_params = 0, words = 0, pre_field = kNoField, topo_field = kNoField, voice0 = 0, voice_end = 0;
     bool has_sample = false;
+    // a kit of voices that each have their own fields (the drum kit): `vparts` repeat voice_slots times in the
+    // fields, slot p's at vparts[].field0 + p * OLFX_VC_NPARAMS, and make one coefficient record of `vwords`
+    // words per voice slot, delivered apart from the kind's own record (`parts`).  0: no such voices
+    uint32_t voice_slots = 0, nvparts = 0, vwords = 0;
+    Part vparts[2] = {};
     uint32_t nset = 0;
     struct { uint8_t field; float value; } set[5] = {};   // defaults that differ from the parts' own
     uint8_t in_ch = 2, out_ch = 2;
@@ -81,6 +86,7 @@ struct Segments {
     uint32_t total() const { return words[0] + words[1] + words[2]; }
 };
 Segments coef_segments(int kind);
+Segments voice_segments(int kind);           // a kit kind's record per voice slot (KindDesc::vparts); else none
 
 // ---- the control packet (u32 words, 16-B aligned sections) ----
 // instance list (absent when every instance changed: dense) | coefficient records [W][m] | event
@@ -88,12 +94,17 @@ Segments coef_segments(int kind);
 struct PacketPlan {
     bool dense;
     size_t o_inst, o_val, o_ev, words;
+    // a kit kind's second section, ahead of the events: the m2 changed voice slots (device slots p * npad + kit,
+    // always listed) and their records [W2][m2]
+    size_t m2 = 0, o_inst2 = 0, o_val2 = 0;
 };
 // n instances of which m changed, W words per record, `evs`: an event section with n_more
 // overflow records for n_ev voice slots (0: the n instances are the voices)
-PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0);
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0, size_t m2 = 0,
+                       uint32_t W2 = 0);
 // The largest packet an engine can produce: every instance's coefficients and, for voices, an
-// event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).
+// event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).  A kit
+// kind: every kit's record, every voice slot's record and an event per voice.
 size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0);
 
 struct Folded { uint32_t inst, op, freq, pad; };
@@ -146,10 +157,18 @@ struct Shadow {
     uint32_t n = 0, n_params = 0;
     float sr = 48000.f;
     std::vector<float> params;            // [n_params][n]
-    std::vector<uint8_t> configured;      // voice: UpdateConfig seen
+    std::vector<uint8_t> configured;      // voice: UpdateConfig seen; a kit kind: per voice slot [voices][n]
     // instances whose coefficients must be re-derived at the next block (each listed once)
     std::vector<uint32_t> dirty_list;
     std::vector<uint8_t> dirty_mark;
+    // a kit kind: the voice slots (p * n + kit) whose record must be re-derived; dirty_list holds the kits whose
+    // rack or sum order changed
+    std::vector<uint32_t> vdirty_list;
+    std::vector<uint8_t> vdirty_mark;
+    // the kit's VoiceMap (VoiceMap.h:27-58): note2voice [128][n] and channel2voice [16][n], kNoVoice = nobody.
+    // Configuration like the bank: reset() keeps it
+    static constexpr uint8_t kNoVoice = 0xFF;
+    std::vector<uint8_t> note2voice, chan2voice;
     int64_t n_components = 0;             // rack instances with OLFX_FR_TOPOLOGY >= 2
     bool pre_changed = true;              // a reverb pre-delay changed since the flag was last cleared
     std::vector<olfx_voice_event> events; // queued for the next block
@@ -179,10 +198,15 @@ struct Shadow {
     void init(int kind_, uint32_t n_, float sr_, uint32_t voices_ = kSynthDefaultVoices) {
         kind = kind_; n = n_; sr = sr_; kd = &kind_desc(kind_); n_params = kd->n_params;
         rf.depth = kind_ == OLFX_KIND_CHORUS ? chorus_history(sr_) : 0u;
-        samples.assign(kd->has_sample ? n_ : 0u, SampleAsg{});
         voices = instruments() ? voices_ : 0u;
         npad = instruments() ? (n_ + 63u) & ~63u : 0u;
+        samples.assign(kd->has_sample ? n_voices() : 0u, SampleAsg{});
+        note2voice.assign(kit() ? (size_t)128 * n_ : 0u, kNoVoice);
+        chan2voice.assign(kit() ? (size_t)16 * n_ : 0u, kNoVoice);
     }
+    bool kit() const { return kd->voice_slots != 0; }
+    // the voices olfx_sample_voices addresses: the instances themselves, or a kit's (kit * voices + p)
+    uint32_t n_voices() const { return kit() ? n * voices : n; }
     bool instruments() const { return kd->instances == KindDesc::INSTRUMENTS; }
     // the voice slots that note events address: the instances themselves, or the synth's voices
     uint32_t n_ev() const { return instruments() ? voices * npad : n; }
@@ -197,6 +221,12 @@ struct Shadow {
     int note_events(const olfx_event *ev, uint32_t count);
     int voice_events(const olfx_voice_event *ev, uint32_t count);
     int synth_playing(uint32_t inst, uint8_t *out);                  // [voices]
+    // olfx_drumkit_map: VoiceMap::SetVoice records in order, judged on the state after the last
+    int drumkit_map(const olfx_drumkit_voice *recs, uint32_t count);
+    // a kit's sum order (DKC_ORDER): its mapped voices by ascending note, four bits each
+    uint32_t order_word(uint32_t kit_) const;
+    // the record of voice slot hv = p * n + kit: its coefficients from its own fields, then its Sample
+    void derive_voice_record(uint32_t hv, uint32_t *w) const;
     bool uniform_predelay() const;        // reverb: every instance has the same pre-delay in samples
     // olfx_sample_bank in two steps, so that the engine can allocate and copy in between: the layout of
     // a valid bank (nothing changes), then the switch to it (every Sample fresh; assignments whose index
@@ -212,7 +242,7 @@ struct Shadow {
     // The queued events as one record per voice (`folded`) and their place in the event section.
     void fold_events();
     PacketPlan plan(bool evs) const {
-        return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev());
+        return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords);
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
@@ -228,6 +258,12 @@ private:
     const char *bad_value(uint32_t field, float v) const;
     void store_param(uint32_t field, uint32_t inst, float v);
     void mark_dirty(uint32_t first, uint32_t count);
+    void mark_vdirty(uint32_t hv);
+    // a write to fields [field0, field0 + n_fields) of instance inst: Update() of the voices it touches (a kit
+    // kind: exactly those voice slots), and what must be re-derived
+    void touched(uint32_t inst, uint32_t field0, uint32_t n_fields);
+    // the kit's VoiceMap router (VoiceMap.h:27-43): a note event -> the event of the voice at that note
+    void route_kit(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // the synth's Polyvoice router (Polyvoice.h:35-77): one instrument event -> per-voice events
     void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())

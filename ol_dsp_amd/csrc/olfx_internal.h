@@ -320,6 +320,29 @@ struct SynthArgs {
 };
 hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
 
+// The drum kit (drumkit.hip): `voices` sample voices per kit, their VoiceMap sum in the order the host
+// derived from the kit's map (DKC_ORDER), the rack at each kit's topology (0 or 1), in one launch.  Voice p
+// of kit i is voice slot p * npad + i of the state, coefficient and Sample planes and of the event slots.
+struct DrumkitArgs {
+    float *ring;                // [n][kFrMaxDelay][2]
+    uint32_t *fr_state;         // [FRS_N][n]
+    const uint32_t *fr_coef;    // [FRC_N][n]
+    float *vc_state;            // [VCS_N][voices * npad]
+    const float *vc_coef;       // [VCC_N][voices * npad]
+    const uint32_t *smp;        // [SMC_N][voices * npad]
+    const uint32_t *order;      // [n]
+    const float *bank;          // bank_bytes bytes (nullptr / 0: no bank)
+    uint32_t bank_bytes;
+    float *out;                 // [2][..][n]
+    uint64_t plane;
+    uint32_t n, n_frames;       // kits; frames (multiple of 4)
+    uint32_t t0;                // rack ring position of the first frame: frames since create mod 48000
+    uint32_t voices, npad;
+    const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
+    const uint2 *ev_more;
+};
+hipError_t launch_drumkit(const DrumkitArgs &a, hipStream_t s);
+
 hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);
 hipError_t launch_chorus(const ChorusArgs &a, hipStream_t s);

@@ -162,6 +162,17 @@ enum {
 enum { VCS_SM_POS = VCS_PHASE, VCS_SM_FLAGS = VCS_PORT_Z };
 
 // ----------------------------------------------------------------------------------------------
+// Drum kit (drumkit.hip): P sample voices per kit behind a VoiceMap.  Every voice slot (p * npad + kit,
+// like the synths' state planes) has its own coefficients [VCC_N], Sample [SMC_N] and state [VCS_N].
+// A kit's sum order is one word ([n]): eight 4-bit voice slots in summing order (VoiceMap::Process: the
+// mapped voices by ascending note), lowest nibble first, kDkOrderEnd = end of the list.
+// ----------------------------------------------------------------------------------------------
+constexpr uint32_t kDkMaxVoices = OLFX_DK_MAX_VOICES;
+constexpr uint32_t kDkOrderEnd = 0xFu;
+constexpr uint32_t kDkOrderEmpty = 0xFFFFFFFFu;     // a kit with an empty map: nothing is summed
+enum { DKC_ORDER = 0, DKC_N };
+
+// ----------------------------------------------------------------------------------------------
 // Effect rack ol::fx::FxRack<2> (fxrack.hip): delay lines + two Svf (channel 0) + ReverbSc stub.
 // ----------------------------------------------------------------------------------------------
 constexpr uint32_t kFrMaxDelay = 48000;     // MAX_DELAY (modules/fxlib/Fx.h:23): ring positions

@@ -33,6 +33,7 @@ KIND_NAMES = {
     "voice_sample": _lib.KIND_VOICE_SAMPLE,
     "synth": _lib.KIND_SYNTH,
     "synth_svf": _lib.KIND_SYNTH_SVF,
+    "drumkit": _lib.KIND_DRUMKIT,
 }
 
 # parameter field names, in C-ABI order
@@ -59,6 +60,9 @@ PARAMS[_lib.KIND_PLATERACK] = PARAMS[_lib.KIND_FXRACK] + ["verb_" + p for p in P
 # the synth: the voices' fields, then the rack's (OLFX_SY_*; the two lists share filter_cutoff and others)
 PARAMS[_lib.KIND_SYNTH] = PARAMS[_lib.KIND_VOICE] + ["rack_" + p for p in PARAMS[_lib.KIND_FXRACK]]
 PARAMS[_lib.KIND_SYNTH_SVF] = PARAMS[_lib.KIND_SYNTH]
+# the drum kit: eight voice slots of the voice's fields ("v3_filter_cutoff"), then the rack's (OLFX_DK_*)
+PARAMS[_lib.KIND_DRUMKIT] = ([f"v{p}_{f}" for p in range(_lib.DK_MAX_VOICES) for f in PARAMS[_lib.KIND_VOICE]]
+                             + ["rack_" + p for p in PARAMS[_lib.KIND_FXRACK]])
 
 
 def kind_info(kind: int, sample_rate: float = 48000.0) -> _lib.KindInfo:
@@ -84,10 +88,14 @@ class Engine:
         self.device = int(device)
         self.info = kind_info(self.kind, sample_rate)
         h = ctypes.c_void_p()
-        if voices is not None:
+        if voices is not None and self.kind == _lib.KIND_DRUMKIT:
+            # voices per kit (olfx_create_drumkit; olfx_create gives 4)
+            check(self.lib.olfx_create_drumkit(self.device, self.n, int(voices), self.sample_rate, self.block,
+                                               ctypes.byref(h)))
+        elif voices is not None:
             # voices per instrument: the synth kinds only (olfx_create_synth_kind; olfx_create gives 4)
             if self.kind not in (_lib.KIND_SYNTH, _lib.KIND_SYNTH_SVF):
-                raise ValueError("voices= is for the synth kinds")
+                raise ValueError("voices= is for the synth kinds and the drum kit")
             check(self.lib.olfx_create_synth_kind(self.kind, self.device, self.n, int(voices), self.sample_rate,
                                                   self.block, ctypes.byref(h)))
         else:
@@ -206,8 +214,9 @@ class Engine:
         check(self.lib.olfx_update(self._h, int(first), int(count)), self._h)
 
     def control(self, events: Iterable[Sequence]) -> None:
-        """Control changes, applied in order: iterable of (inst, cc, value[, source]); source
-        "midi" (value 0..127, the default) or "hw" (UpdateHardwareControl value)."""
+        """Control changes, applied in order: iterable of (inst, cc, value[, source[, channel]]); source
+        "midi" (value 0..127, the default) or "hw" (UpdateHardwareControl value); channel (the drum kit only):
+        the MIDI channel 0..15 whose voice takes the control, or _lib.DK_CHANNEL_RACK for the kit's rack."""
         evs = list(events)
         if not evs:
             return
@@ -217,9 +226,26 @@ class Engine:
             arr[k].control = int(e[1])
             arr[k].value = float(e[2])
             arr[k].source = _lib.CTL_HARDWARE if len(e) > 3 and e[3] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
+            arr[k].pad = int(e[4]) if len(e) > 4 else 0
         check(self.lib.olfx_control(self._h, arr, len(evs)), self._h)
 
-    # ---- the synth's Polyvoice (OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF) ----
+    # ---- the drum kit's VoiceMap (OLFX_KIND_DRUMKIT) ----
+    def drumkit_map(self, records: Iterable[Sequence]) -> None:
+        """VoiceMap::SetVoice records in order: iterable of (kit, channel, note, voice); voice None clears the
+        entries, channel or note None leaves that table alone (olfx_drumkit_map).  A call that would leave a
+        voice at two notes is refused and changes nothing."""
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.DrumkitVoice * len(recs))()
+        for k, (kit, channel, note, voice) in enumerate(recs):
+            arr[k].kit = int(kit)
+            arr[k].channel = _lib.DK_NO_CHANNEL if channel is None else int(channel)
+            arr[k].note = _lib.DK_NO_NOTE if note is None else int(note)
+            arr[k].voice = _lib.DK_NO_VOICE if voice is None else int(voice)
+        check(self.lib.olfx_drumkit_map(self._h, arr, len(recs)), self._h)
+
+    # ---- the synth's Polyvoice (OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF) and the drum kit's voices ----
     @property
     def voices(self) -> int:
         """Voices per instrument (0 for other kinds)."""

@@ -44,6 +44,8 @@ RANGES["platerack"] = RANGES["fxrack"] + RANGES["dattorro_rpd"]
 RANGES["synth"] = RANGES["voice"] + RANGES["fxrack"][:-1] + [1.0]
 # the Svf synth: the same fields, each instrument's rack topology drawn from {0, 1}
 RANGES["synth_svf"] = RANGES["voice"] + RANGES["fxrack"][:-1] + ["int2"]
+# the drum kit: eight voice slots, each pad with its own draw, then the rack's with the topology from {0, 1}
+RANGES["drumkit"] = 8 * RANGES["voice"] + RANGES["fxrack"][:-1] + ["int2"]
 
 
 def _splitmix64(z: np.ndarray) -> np.ndarray:
