@@ -543,6 +543,23 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.mode = mode;
         return a;
     };
+    // what the fused instrument kinds share (synth, Svf synth, drum kit)
+    auto instrument_args = [&](InstrumentArgs &a) {
+        a.ring = e->fr_ring;
+        a.fr_state = e->fr_state;
+        a.fr_coef = e->fr_coef;
+        a.vc_state = e->vc_state;
+        a.vc_coef = e->vc_coef;
+        a.out = dout;
+        a.plane = plane;
+        a.n = e->n;
+        a.n_frames = n_frames;
+        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
+        a.voices = e->hs.voices;
+        a.npad = e->hs.npad;
+        a.ev = ev.ev;
+        a.ev_more = ev.ev_more;
+    };
     switch (e->kind) {
     case OLFX_KIND_DATTORRO: {
         if (e->hs.pre_changed) {
@@ -626,20 +643,7 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
     case OLFX_KIND_SYNTH_SVF: {
         // one fused launch: the voice waves feed the delay waves and the filter wave through LDS
         SynthArgs a{};
-        a.ring = e->fr_ring;
-        a.fr_state = e->fr_state;
-        a.fr_coef = e->fr_coef;
-        a.vc_state = e->vc_state;
-        a.vc_coef = e->vc_coef;
-        a.out = dout;
-        a.plane = plane;
-        a.n = e->n;
-        a.n_frames = n_frames;
-        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
-        a.voices = e->hs.voices;
-        a.npad = e->hs.npad;
-        a.ev = ev.ev;
-        a.ev_more = ev.ev_more;
+        instrument_args(a);
         a.svf = e->kind == OLFX_KIND_SYNTH_SVF;
         r = launch_synth(a, s);
         break;
@@ -647,24 +651,11 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
     case OLFX_KIND_DRUMKIT: {
         // one fused launch: the sample-voice waves feed the delay waves and the filter wave through LDS
         DrumkitArgs a{};
-        a.ring = e->fr_ring;
-        a.fr_state = e->fr_state;
-        a.fr_coef = e->fr_coef;
-        a.vc_state = e->vc_state;
-        a.vc_coef = e->vc_coef;
+        instrument_args(a);
         a.smp = e->sm_asg;
         a.order = e->dk_order;
         a.bank = e->sm_bank;
         a.bank_bytes = (uint32_t)e->sm_bank_bytes;
-        a.out = dout;
-        a.plane = plane;
-        a.n = e->n;
-        a.n_frames = n_frames;
-        a.t0 = (uint32_t)(e->frames % kFrMaxDelay);
-        a.voices = e->hs.voices;
-        a.npad = e->hs.npad;
-        a.ev = ev.ev;
-        a.ev_more = ev.ev_more;
         r = launch_drumkit(a, s);
         break;
     }

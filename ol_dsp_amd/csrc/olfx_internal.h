@@ -296,19 +296,15 @@ struct PlateRackArgs {
 };
 hipError_t launch_platerack(const PlateRackArgs &a, hipStream_t s);
 
-// The synth (synth.hip): `voices` MoogFilter SynthVoices per instrument, their Polyvoice sum, the
-// rack's topology 1, in one launch.  Voice p of instrument i is voice slot p * npad + i of the state
-// planes and the event slots (npad = n rounded up to 64: a 64-voice group is one voice slot of 64
-// consecutive instruments); the voice coefficients are the instrument's ([VCC_N][n]: Polyvoice fans
-// every setter out to all its voices).
-// svf = 1 (OLFX_KIND_SYNTH_SVF): SvfFilter voices (state planes [VCS_N]) and the rack at each instrument's
-// topology, 0 or 1 (FRC_TOPO).
-struct SynthArgs {
+// What the fused instrument kernels share (synth_pipeline.h): the rack's planes, the voices' planes, the
+// output and the block.  Voice p of instrument i is voice slot p * npad + i of the state planes and the event
+// slots (npad = n rounded up to 64: a 64-voice group is one voice slot of 64 consecutive instruments).
+struct InstrumentArgs {
     float *ring;                // [n][kFrMaxDelay][2]
     uint32_t *fr_state;         // [FRS_N][n]
     const uint32_t *fr_coef;    // [FRC_N][n]
-    float *vc_state;            // [VCS_N_MOOG][voices * npad]; svf: [VCS_N][voices * npad]
-    const float *vc_coef;       // [VCC_N][n]
+    float *vc_state;            // [..][voices * npad]: synth [VCS_N_MOOG], svf synth and drum kit [VCS_N]
+    const float *vc_coef;       // synth: [VCC_N][n]; drum kit: [VCC_N][voices * npad]
     float *out;                 // [2][..][n]
     uint64_t plane;
     uint32_t n, n_frames;       // instruments; frames (multiple of 4)
@@ -316,30 +312,31 @@ struct SynthArgs {
     uint32_t voices, npad;
     const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
     const uint2 *ev_more;
+};
+// what both launches require of a non-empty block
+inline bool instrument_args_ok(const InstrumentArgs &a, uint32_t max_voices) {
+    return !(a.n_frames & 3u) && !(a.t0 & 1u) && a.t0 < kFrMaxDelay && a.voices >= 1u && a.voices <= max_voices &&
+           a.npad == ((a.n + 63u) & ~63u) && a.plane >= (uint64_t)a.n_frames * a.n;
+}
+
+// The synth (synth.hip): `voices` MoogFilter SynthVoices per instrument, their Polyvoice sum, the
+// rack's topology 1, in one launch.  The voice coefficients are the instrument's (Polyvoice fans
+// every setter out to all its voices).
+// svf = 1 (OLFX_KIND_SYNTH_SVF): SvfFilter voices (state planes [VCS_N]) and the rack at each instrument's
+// topology, 0 or 1 (FRC_TOPO).
+struct SynthArgs : InstrumentArgs {
     uint32_t svf;               // 1: synth_svf_block_v1
 };
 hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
 
 // The drum kit (drumkit.hip): `voices` sample voices per kit, their VoiceMap sum in the order the host
-// derived from the kit's map (DKC_ORDER), the rack at each kit's topology (0 or 1), in one launch.  Voice p
-// of kit i is voice slot p * npad + i of the state, coefficient and Sample planes and of the event slots.
-struct DrumkitArgs {
-    float *ring;                // [n][kFrMaxDelay][2]
-    uint32_t *fr_state;         // [FRS_N][n]
-    const uint32_t *fr_coef;    // [FRC_N][n]
-    float *vc_state;            // [VCS_N][voices * npad]
-    const float *vc_coef;       // [VCC_N][voices * npad]
+// derived from the kit's map (DKC_ORDER), the rack at each kit's topology (0 or 1), in one launch.  A voice
+// slot has its own coefficients and Sample planes.
+struct DrumkitArgs : InstrumentArgs {
     const uint32_t *smp;        // [SMC_N][voices * npad]
     const uint32_t *order;      // [n]
     const float *bank;          // bank_bytes bytes (nullptr / 0: no bank)
     uint32_t bank_bytes;
-    float *out;                 // [2][..][n]
-    uint64_t plane;
-    uint32_t n, n_frames;       // kits; frames (multiple of 4)
-    uint32_t t0;                // rack ring position of the first frame: frames since create mod 48000
-    uint32_t voices, npad;
-    const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
-    const uint2 *ev_more;
 };
 hipError_t launch_drumkit(const DrumkitArgs &a, hipStream_t s);
 

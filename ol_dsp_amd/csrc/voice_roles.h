@@ -159,6 +159,37 @@ struct Env {
     }
 };
 
+// The envelopes and the gate of a voice that one lane holds for a whole block (synth.hip, drumkit.hip).
+struct VoiceEnvs {
+    Env ea, ef;
+    bool gate, gprev_a, gprev_f;
+};
+// Voice slot si of state planes of stride sn, with the coefficients at ci of planes of stride cn: the flag word
+// and levels, the block's gate events of `group` on them (returned for the caller's own events), both
+// Env::begin.  The state loads are issued before the event read, as voice_role_env's.
+__device__ __forceinline__ VoiceEv voice_envs_load(VoiceEnvs &v, const float *s, uint32_t sn, uint32_t si, const float *c,
+                                                   uint32_t cn, uint32_t ci, const uint2 *evs, const uint2 *evs_more,
+                                                   uint2 *slot, uint32_t lane, uint32_t me, uint32_t group) {
+    uint32_t flags0 = __float_as_uint(s[VCS_FLAGS * sn + si]);
+    float xa0 = s[VCS_ENVA_X * sn + si], xf0 = s[VCS_ENVF_X * sn + si];
+    const VoiceEv ev = voice_event_of(evs, evs_more, slot, lane, me, group);
+    apply_gate_events(ev, flags0, xa0, xf0);
+    v.gate = (flags0 >> 8) & 1u;
+    v.gprev_a = (flags0 >> 6) & 1u;
+    v.gprev_f = (flags0 >> 7) & 1u;
+    v.ea.begin(v.gate, v.gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * cn + ci], c[VCC_ATK_TGT_A * cn + ci],
+               c[VCC_DEC_D0A * cn + ci], c[VCC_REL_D0A * cn + ci], c[VCC_SUS_A * cn + ci]);
+    v.ef.begin(v.gate, v.gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * cn + ci], c[VCC_ATK_TGT_F * cn + ci],
+               c[VCC_DEC_D0F * cn + ci], c[VCC_REL_D0F * cn + ci], c[VCC_SUS_F * cn + ci]);
+    return ev;
+}
+__device__ __forceinline__ void voice_envs_store(const VoiceEnvs &v, float *s, uint32_t sn, uint32_t si) {
+    s[VCS_ENVA_X * sn + si] = v.ea.x;
+    s[VCS_ENVF_X * sn + si] = v.ef.x;
+    s[VCS_FLAGS * sn + si] = __uint_as_float(v.ea.mode | v.ef.mode << 3 | (uint32_t)v.gprev_a << 6 |
+                                             (uint32_t)v.gprev_f << 7 | (uint32_t)v.gate << 8);
+}
+
 // samples per hand-off between the roles: 8 (34 barrier steps per 256-frame block, pipeline fill
 // 2 of them) measured 2 % faster than 16 (18 steps) for the Svf voice and equal for the Moog
 // voice; 32 halves the workgroups per CU (96 KB of LDS each) and is 1.7x slower

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Compile one .hip file for gfx950 with saved temps and report, per kernel: VGPR/AGPR/spills,
 instruction mix, and scratch (spill) instructions inside loops.
+A file that the Makefile beside it lists in NOSLP_SRCS is compiled with the Makefile's NOSLP flag, as shipped.
 Usage: python tools/isa_report.py ol_dsp_amd/csrc/chorus.hip [kernel-substring] [-DX=Y ...]"""
 import collections, os, re, subprocess, sys, tempfile
 
@@ -8,9 +9,13 @@ src = sys.argv[1]
 sub = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("-D") else ""
 defs = [a for a in sys.argv[2:] if a.startswith("-D")]
 sub = "" if sub == "-v" else sub
+mk = os.path.join(os.path.dirname(os.path.abspath(src)), "Makefile")
+mk = open(mk).read() if os.path.exists(mk) else ""
+var = lambda k: (re.search(r"^" + k + r"\s*=\s*(.*)$", mk, flags=re.M) or [None, ""])[1].split()
+noslp = var("NOSLP") if os.path.basename(src) in var("NOSLP_SRCS") else []
 d = tempfile.mkdtemp()
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                "-fno-gpu-flush-denormals-to-zero", "--save-temps", "-c", os.path.abspath(src), "-o", os.path.join(d, "x.o")] + defs,
+                "-fno-gpu-flush-denormals-to-zero", "--save-temps", "-c", os.path.abspath(src), "-o", os.path.join(d, "x.o")] + noslp + defs,
                cwd=d, check=True, capture_output=True)
 asm = [f for f in os.listdir(d) if f.endswith("gfx950.s")][0]
 s = open(os.path.join(d, asm)).read()
@@ -40,7 +45,7 @@ for m in re.finditer(r"^(_Z\w+):", s, flags=re.M):
     c = collections.Counter(i.split()[0] for i in ins)
     meta = s[s.find(".name:           " + name):][:2000]
     g = lambda k: (re.search(r"\." + k + r":\s+(\d+)", meta) or [None, "?"])[1]
-    print(f"{name}: vgpr {g('vgpr_count')} agpr {g('agpr_count')} vspill {g('vgpr_spill_count')} sspill {g('sgpr_spill_count')} "
+    print(f"{name}: vgpr {g('vgpr_count')} agpr {g('agpr_count')} sgpr {g('sgpr_count')} vspill {g('vgpr_spill_count')} sspill {g('sgpr_spill_count')} "
           f"| valu {sum(v for k, v in c.items() if k.startswith('v_'))} lds {sum(v for k, v in c.items() if k.startswith('ds_'))} "
           f"vmem {sum(v for k, v in c.items() if k.startswith(('buffer_', 'global_')))} scratch {sum(v for k, v in c.items() if 'scratch' in k)} "
           f"(in loops {inloop}) vmcnt(0) in loops {w0loop}")
