@@ -108,7 +108,7 @@ enum {
                                   (olfx_create_synth_kind).  OLFX_SY_* fields; rules below. */
     /* 13 stays unassigned: tests/cpp/dump_kinds.cpp (tests/golden/host_kinds.txt), tests/cpp/test_synth_svf_host.cpp
        and tests/test_synth_svf_host.py pin it as "a kind nobody has" (OLFX_E_KIND) */
-    OLFX_KIND_DRUMKIT = 14     /* the reference's drum machine, one launch (drumkit.hip): per kit, P sample voices
+    OLFX_KIND_DRUMKIT = 14,    /* the reference's drum machine, one launch (drumkit.hip): per kit, P sample voices
                                   (SynthVoice(SampleSoundSource<1>(Sample), SvfFilter), OLFX_KIND_VOICE_SAMPLE's, each
                                   with its own Voice::Config and Sample) behind a VoiceMap (VoiceMap.h:27-82), into
                                   the rack at the kit's OLFX_FR_TOPOLOGY, 0 or 1 as OLFX_KIND_SYNTH_SVF:
@@ -120,6 +120,14 @@ enum {
                                   ascending note order + OLFX_KIND_FXRACK at that topology give for the sum in input
                                   channel 0 and zeros in channel 1.  P = 4 (olfx_create) or 1..8 (olfx_create_drumkit).
                                   OLFX_DK_* fields, olfx_drumkit_map; rules below. */
+    OLFX_KIND_METER = 15,      /* a level meter on the device (meter.hip): per signal -- one channel of one instance
+                                  -- ol::core::Rms (corelib/ol_corelib.h:61-85) paired with the peak-hold follower of
+                                  its one caller, the sandbox firmware's callback (ol_daisy/workouts/sandbox/
+                                  main.cpp:98-137).  In [2][n_frames][n_inst], the effect and instrument kinds' output;
+                                  the two channels are independent signals.  out [2][n_frames][n_inst] = the value
+                                  Rms::Process returns at each frame, or NULL: levels only (olfx_meter_read).
+                                  OLFX_MT_* fields; rules below. */
+    OLFX_KIND_METER_MONO = 16  /* the same over [n_frames][n_inst]: the voice kinds' output, or olfx_mix's buses */
 };
 
 /* ---- parameters (field index, value is what the reference setter takes) ---- */
@@ -318,6 +326,31 @@ enum {
 #define OLFX_DK_NO_CHANNEL   0xFFu         /* olfx_drumkit_voice.channel: leave channel2voice alone (an extension) */
 #define OLFX_DK_CHANNEL_RACK 16            /* olfx_control_event.pad: the kit's rack */
 
+/* Level meter (OLFX_KIND_METER, OLFX_KIND_METER_MONO): two fields per instance, shared by its channels.
+   Per signal the state is five floats, all 0 after create and olfx_reset; per frame with input x, in this order:
+     if (count == window) { sum = 0; count = 0; }          before the add (ol_corelib.h:76-79)
+     sum = sum + x * x;  count = count + 1.0f;
+     rms = sqrtf(sum / count);                              what Rms::Process returns
+     peak = (peak < fabsf(x)) ? fabsf(x) : peak;            sandbox/main.cpp:132
+     peak_count = peak_count + 1.0f;
+     if (peak_count == hold) { peak_count = 0; peak = 0; }  :133-137
+   all in fp32, the counters included (t_sample sample_count, t_sample peak_hold), no contraction.  The firmware
+   writes abs(...); it is taken as fabsf here.  What follows from fp32 counters is kept: a window that is no whole
+   number (Init(44100): 44100 / 375 = 117.6) or lies below the running count never matches, so the sum grows for
+   ever; a NaN sample poisons rms until the next window reset and never enters peak (the compare is false).
+     OLFX_MT_WINDOW     what Rms::Init(sample_rate, window) takes: 0 = sample_rate / 375 in fp32; default 0.
+                        Setting it is Init again: the window changes, nothing is reset
+     OLFX_MT_PEAK_HOLD  the firmware's peak_hold, default 96000 (2 * 48000, a literal: it does not follow the rate)
+   Any finite value is accepted (a negative or fractional one never matches); a non-finite one is OLFX_E_ARG.  A
+   change lands at the next block boundary like every parameter.  olfx_reset clears the state and keeps both
+   fields (configuration, as a voice engine's buses are).  No control maps to a meter: olfx_control_map
+   and olfx_control are OLFX_E_KIND.
+   olfx_process with out == NULL (these two kinds only) is summary mode: the state advances, nothing is written
+   per frame, and rms is that of the call's last frame (the member is overwritten every frame, so no other is
+   observable).  It reads 4 B per signal-frame, half of what olfx_algorithmic_bytes_per_frame reports (the
+   envelope mode's 4 B in + 4 B out).  The two modes leave the same state in any alternation, bit for bit. */
+enum { OLFX_MT_WINDOW = 0, OLFX_MT_PEAK_HOLD, OLFX_MT_NPARAMS };
+
 /* ---- note events (voices) ----
    The ol::synth::Voice calls that change a voice's gate or pitch (Voice.h:33-57), as SynthVoice
    implements them (SynthVoice.h:231-268):
@@ -490,7 +523,8 @@ int olfx_update(olfx_engine *e, uint32_t first, uint32_t count);
 
 /* Process n_frames (multiple of 4) for all instances.  `stream` is a hipStream_t; NULL is the
    HIP default (null) stream, as everywhere in HIP; olfx_stream(e) is the engine's own stream.
-   With OLFX_IO_DEVICE the call is asynchronous on that stream. */
+   With OLFX_IO_DEVICE the call is asynchronous on that stream.  out == NULL is OLFX_E_ARG, except on the
+   level-meter kinds, where it selects their summary mode (OLFX_MT_*, above). */
 int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames, int io_flags,
                  void *stream);
 
@@ -544,6 +578,13 @@ int olfx_sample_bank(olfx_engine *e, uint32_t n_samples, const uint64_t *offsets
 int olfx_sample_voices(olfx_engine *e, const olfx_sample_voice *recs, uint32_t n);
 /* OLFX_KIND_DRUMKIT: apply n VoiceMap records (above); OLFX_E_STATE on another kind. */
 int olfx_drumkit_map(olfx_engine *e, const olfx_drumkit_voice *recs, uint32_t n);
+
+/* ---- level meters (OLFX_KIND_METER, OLFX_KIND_METER_MONO) ----
+   The five state floats of every channel of instances [first, first + count), copied to the host:
+   levels[(k * channels) + c] is channel c of instance first + k.  Waits for this engine's queued work only (as
+   olfx_reset).  OLFX_E_STATE on another kind. */
+typedef struct olfx_meter_level { float rms, peak, sum, count, peak_count; } olfx_meter_level;
+int olfx_meter_read(olfx_engine *e, uint32_t first, uint32_t count, olfx_meter_level *levels /*[count][channels]*/);
 
 /* Block until all work queued by this engine is done (engine-scoped, see olfx_reset). */
 int olfx_sync(olfx_engine *e);

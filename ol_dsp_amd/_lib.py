@@ -35,6 +35,12 @@ KIND_VOICE_SAMPLE = 10      # 9 is unassigned (olfx.h)
 KIND_SYNTH = 11
 KIND_SYNTH_SVF = 12
 KIND_DRUMKIT = 14           # 13 is unassigned (olfx.h)
+KIND_METER = 15
+KIND_METER_MONO = 16
+
+MT_WINDOW = 0
+MT_PEAK_HOLD = 1
+MT_NPARAMS = 2
 
 DK_MAX_VOICES = 8
 DK_VOICE0 = 0
@@ -127,6 +133,16 @@ class DrumkitVoice(ctypes.Structure):
     ]
 
 
+class MeterLevel(ctypes.Structure):
+    _fields_ = [
+        ("rms", ctypes.c_float),
+        ("peak", ctypes.c_float),
+        ("sum", ctypes.c_float),
+        ("count", ctypes.c_float),
+        ("peak_count", ctypes.c_float),
+    ]
+
+
 CTL_MIDI = 0
 CTL_HARDWARE = 1
 IGNORED = 1
@@ -179,6 +195,7 @@ SIGNATURES = {
     "olfx_sample_bank": (ctypes.c_int, [_P, _U32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_F)]),
     "olfx_sample_voices": (ctypes.c_int, [_P, ctypes.POINTER(SampleVoice), _U32]),
     "olfx_drumkit_map": (ctypes.c_int, [_P, ctypes.POINTER(DrumkitVoice), _U32]),
+    "olfx_meter_read": (ctypes.c_int, [_P, _U32, _U32, ctypes.POINTER(MeterLevel)]),
     # include/olfx_sample.h: per-instance, per-sample operators (one block of latency)
     "olfx_sample_pool_config": (ctypes.c_int, [ctypes.c_int, _U32]),
     "olfx_sample_pool_config_depth": (ctypes.c_int, [ctypes.c_int, _U32, _U32]),

@@ -141,6 +141,8 @@ struct olfx_engine {
     // the drum kit: each kit's sum order ([n], DKC_ORDER); its voices' planes are vc_state, vc_coef and sm_asg
     // over the voice slots
     uint32_t *dk_order = nullptr;
+    // the level meters: every signal's five floats ([MTS_N][channels * n]) and each instance's window and hold
+    float *mt_state = nullptr, *mt_coef = nullptr;
     // voice buses (olfx_mix_config): [n_buses + 1] offsets, then the voice lists
     uint32_t *mix_dev = nullptr;
     uint32_t mix_quad = 0;                  // contiguous buses on multiples of 4 voices (voice_mix_v4)
@@ -230,6 +232,10 @@ size_t carve(olfx_engine *e, char *base) {
         take(e->sm_asg, (size_t)SMC_N * slots * 4);
         take(e->dk_order, (size_t)DKC_N * n * 4);
     }
+    if (is_meter_kind(kind)) {
+        take(e->mt_state, (size_t)MTS_N * in_channels(kind) * n * 4);
+        take(e->mt_coef, (size_t)MTC_N * n * 4);
+    }
     return off;
 }
 
@@ -253,6 +259,7 @@ uint32_t coef_segments(const olfx_engine *e, CoefScatterArgs *a, bool voice_slot
         /* TO_FR */ {e->fr_coef, e->n},
         /* TO_SM */ {e->sm_asg, nv},
         /* TO_ORD */ {e->dk_order, e->n},
+        /* TO_MT */ {e->mt_coef, e->n},
     };
     const host::Segments sg = voice_slots ? host::voice_segments(e->kind) : host::coef_segments(e->kind);
     const host::Part *parts = voice_slots ? kd.vparts : kd.parts;
@@ -659,6 +666,21 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         r = launch_drumkit(a, s);
         break;
     }
+    case OLFX_KIND_METER:
+    case OLFX_KIND_METER_MONO: {
+        // dout null: summary mode
+        MeterArgs a{};
+        a.in = din;
+        a.out = dout;
+        a.state = e->mt_state;
+        a.coef = e->mt_coef;
+        a.plane = plane;
+        a.n = e->n;
+        a.n_frames = n_frames;
+        a.planes = in_channels(e->kind);
+        r = launch_meter(a, s);
+        break;
+    }
     case OLFX_KIND_CHAIN: {
         // one fused launch: chorus and pitch-shift waves feed the reverb wave through LDS
         ChainArgs a{};
@@ -971,19 +993,21 @@ int olfx_update(olfx_engine *e, uint32_t first, uint32_t count) {
 int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames, int io_flags, void *stream) {
     if (!e) return OLFX_E_ARG;
     if (n_frames == 0) return OLFX_OK;
-    if ((n_frames & 3u) || !out || (in_channels(e->kind) && !in))
+    // (a meter without `out` runs its summary mode)
+    const bool summary = !out && is_meter_kind(e->kind);
+    if ((n_frames & 3u) || (!out && !summary) || (in_channels(e->kind) && !in))
         return e->fail(OLFX_E_ARG, "olfx_process: bad argument (n_frames=%u must be a multiple of 4)", n_frames);
     if (io_flags != OLFX_IO_DEVICE && io_flags != OLFX_IO_HOST)
         return e->fail(OLFX_E_ARG, "olfx_process: bad io_flags");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;   // NULL = the HIP default (null) stream
     const size_t fin = (size_t)in_channels(e->kind) * n_frames * e->n;
-    const size_t fout = (size_t)out_channels(e->kind) * n_frames * e->n;
+    const size_t fout = summary ? 0 : (size_t)out_channels(e->kind) * n_frames * e->n;
     // a stream switch: this block's work (the control scatter included) after the previous launch
     int rc = order_after_last(e, s);
     if (rc) return rc;
     if (io_flags == OLFX_IO_HOST) {
-        rc = ensure_staging(e, fin ? fin : 1, fout);
+        rc = ensure_staging(e, fin ? fin : 1, fout ? fout : 1);
         if (rc) return rc;
     }
     // the block's parameter changes and note events: asynchronous, O(changed)
@@ -997,7 +1021,7 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
             std::memcpy(e->h_in, in, fin * 4);
             r = hipMemcpyAsync(e->d_in, e->h_in, fin * 4, hipMemcpyHostToDevice, s);
         }
-        rc = r == hipSuccess ? run_frames(e, fin ? e->d_in : nullptr, e->d_out, n_frames, s, ev)
+        rc = r == hipSuccess ? run_frames(e, fin ? e->d_in : nullptr, summary ? nullptr : e->d_out, n_frames, s, ev)
                              : e->hip_fail(r, "olfx_process: input copy");
     } else {
         rc = run_frames(e, in, out, n_frames, s, ev);
@@ -1011,10 +1035,33 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
     }
     if (rc) return rc;
     if (io_flags == OLFX_IO_HOST) {
-        HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out, fout * 4, hipMemcpyDeviceToHost, s));
+        if (fout) HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out, fout * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(e, hipStreamSynchronize(s));
-        std::memcpy(out, e->h_out, fout * 4);
+        if (fout) std::memcpy(out, e->h_out, fout * 4);
     }
+    return OLFX_OK;
+}
+
+// ---- level meters: the state rows of a range of instances, on the host ----
+int olfx_meter_read(olfx_engine *e, uint32_t first, uint32_t count, olfx_meter_level *levels) {
+    if (!e) return OLFX_E_ARG;
+    if (!is_meter_kind(e->kind)) return e->fail(OLFX_E_STATE, "olfx_meter_read: not a meter engine");
+    if ((uint64_t)first + count > e->n || (count && !levels)) return e->fail(OLFX_E_ARG, "olfx_meter_read: range out of bounds");
+    if (!count) return OLFX_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (const int rc = wait_engine(e)) return rc;               // this engine's queued blocks only
+    const uint32_t ch = in_channels(e->kind);
+    const size_t signals = (size_t)ch * e->n;
+    std::vector<float> rows((size_t)MTS_N * ch * count);
+    for (uint32_t f = 0; f < MTS_N; ++f)
+        for (uint32_t c = 0; c < ch; ++c)
+            HIPCHK(e, hipMemcpy(rows.data() + ((size_t)f * ch + c) * count, e->mt_state + f * signals + (size_t)c * e->n + first,
+                                (size_t)count * 4, hipMemcpyDeviceToHost));
+    auto row = [&](uint32_t f, uint32_t c, uint32_t k) { return rows[((size_t)f * ch + c) * count + k]; };
+    for (uint32_t k = 0; k < count; ++k)
+        for (uint32_t c = 0; c < ch; ++c)
+            levels[(size_t)k * ch + c] = olfx_meter_level{row(MTS_RMS, c, k), row(MTS_PEAK, c, k), row(MTS_SUM, c, k),
+                                                          row(MTS_COUNT, c, k), row(MTS_PEAK_COUNT, c, k)};
     return OLFX_OK;
 }
 

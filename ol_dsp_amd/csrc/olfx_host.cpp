@@ -117,6 +117,11 @@ void rack_defaults(float *p) {
     p[OLFX_FR_TOPOLOGY] = 0.f;
 }
 
+void meter_defaults(float *p) {
+    p[OLFX_MT_WINDOW] = 0.0f;                // Rms::Init's default argument (ol_corelib.h:71)
+    p[OLFX_MT_PEAK_HOLD] = 2 * 48000;        // sandbox/main.cpp:101, a literal
+}
+
 }  // namespace
 
 void chorus_sizes(float sr, uint32_t *psize, uint32_t *csize) {
@@ -329,6 +334,14 @@ void derive_voice(const float *p, bool configured, bool moog, float sr, uint32_t
     std::memcpy(w, c, sizeof c);
 }
 
+// Rms::Init (ol_corelib.h:71-73): window_ = window != 0 ? window : sample_rate / 375, in t_sample; the
+// firmware's peak_hold as it is
+void derive_meter(const float *p, float sr, uint32_t *c) {
+    const float window = p[OLFX_MT_WINDOW];
+    c[MTC_WINDOW] = as_u32(window != 0 ? window : sr / 375);
+    c[MTC_HOLD] = as_u32(p[OLFX_MT_PEAK_HOLD]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The components and the kind table: each kind is stated once, here.  The per-kind functions below, the
 // shadow (through the row it looks up in init) and olfx_engine.cpp (scatter destinations, plane
@@ -363,9 +376,11 @@ constexpr Component kComponents[CP_COUNT] = {
     // a kit's sum order: no parameters, its word comes from olfx_drumkit_map
     /* CP_ORDER  */ {0, DKC_N, nullptr,
                      [](const float *, const Shadow &s, uint32_t i, uint32_t *w) { w[DKC_ORDER] = s.order_word(i); }},
+    /* CP_METER  */ {OLFX_MT_NPARAMS, MTC_N, meter_defaults,
+                     [](const float *p, const Shadow &s, uint32_t, uint32_t *w) { derive_meter(p, s.sr, w); }},
 };
 
-constexpr size_t kKinds = OLFX_KIND_DRUMKIT + 1;       // kind numbers 0 .. the last; 0, 9 and 13 are no kinds
+constexpr size_t kKinds = OLFX_KIND_METER_MONO + 1;       // kind numbers 0 .. the last; 0, 9 and 13 are no kinds
 
 constexpr std::array<KindDesc, kKinds> kKindTable = [] {
     std::array<KindDesc, kKinds> t{};
@@ -473,6 +488,16 @@ constexpr std::array<KindDesc, kKinds> kKindTable = [] {
     k->has_sample = true;
     k->set[k->nset++] = {OLFX_DK_RACK0 + OLFX_FR_TOPOLOGY, 1.f};
     k->topologies = 0x3; k->topology_msg = "drum kit rack topology must be 0 or 1";
+    // the level meters: a pure stream.  The figures are the envelope mode's; summary mode (out == NULL) writes
+    // nothing and moves the read share alone, half of the row's figure
+    k = &row(OLFX_KIND_METER, {{CP_METER, 0, TO_MT}}, "meter_block_v1",
+             16.0,                        // 2 x (4 B in + 4 B rms out)
+             8.0);                        // the input
+    k->no_controls = true; k->reset_keeps_params = true;
+    k = &row(OLFX_KIND_METER_MONO, {{CP_METER, 0, TO_MT}}, "meter_block_v1",
+             8.0,                         // 4 B in + 4 B rms out
+             4.0);
+    k->in_ch = 1; k->out_ch = 1; k->no_controls = true; k->reset_keeps_params = true;
     return t;
 }();
 
@@ -539,6 +564,8 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
         case CP_VOICE: bytes += ((uint64_t)VCC_N * 4 + voices * (k.moog ? VCS_N_MOOG : VCS_N) * 4) * n; break;
         case CP_RACK: bytes += ((uint64_t)kFrMaxDelay * 2 * 4 + FRS_N * 4 + FRC_N * 4) * n; break;
         case CP_SAMPLE: bytes += (uint64_t)SMC_N * 4 * n; break;
+        // every channel's five floats, one set of coefficients per instance
+        case CP_METER: bytes += ((uint64_t)MTS_N * k.in_ch + MTC_N) * 4 * n; break;
         default: break;
         }
     // a kit's voices: each its own state, coefficients and Sample words
@@ -589,11 +616,14 @@ int Shadow::fail(int code, const char *fmt, ...) {
 }
 
 void Shadow::reset() {
-    params.assign((size_t)n_params * n, 0.f);
-    float d[kMaxParams];
-    default_params(kind, d);
-    for (uint32_t f = 0; f < n_params; ++f)
-        std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
+    // (a meter's window and hold outlive a reset, as its owner's Init and peak_hold outlive a cleared level)
+    if (!kd->reset_keeps_params || params.size() != (size_t)n_params * n) {
+        params.assign((size_t)n_params * n, 0.f);
+        float d[kMaxParams];
+        default_params(kind, d);
+        for (uint32_t f = 0; f < n_params; ++f)
+            std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
+    }
     configured.assign(kit() ? (size_t)voices * n : n, 0);
     vdirty_list.clear();
     vdirty_mark.assign(kit() ? (size_t)voices * n : 0u, 0);
@@ -966,6 +996,7 @@ int route_control(const KindDesc &kd, uint32_t topology, uint8_t control, int so
 }  // namespace
 
 int Shadow::control(const olfx_control_event *ev, uint32_t count) {
+    if (kd->no_controls) return fail(OLFX_E_KIND, "olfx_control: no control maps to this kind");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_control: null events");
     for (uint32_t k = 0; k < count; ++k) {
         if (ev[k].inst >= n) return fail(OLFX_E_ARG, "olfx_control: event %u: instance out of range", k);
@@ -1317,7 +1348,7 @@ extern "C" int olfx_control_map(int kind, uint8_t control, int source, float val
     const KindDesc &kd = kind_desc(kind);
     // the synths' controls can hit two fields: olfx_synth_control_map / olfx_synth_control_map_at; the drum
     // kit's need a channel
-    if (kd.instances == KindDesc::INSTRUMENTS) return OLFX_E_KIND;
+    if (kd.instances == KindDesc::INSTRUMENTS || kd.no_controls) return OLFX_E_KIND;
     uint32_t f[2];
     float v[2];
     const int hits = route_control(kd, 0u, control, source, value, f, v);

@@ -17,9 +17,9 @@ namespace host __attribute__((visibility("hidden"))) {
 
 // ---- components and kinds (the table is in olfx_host.cpp) ----
 // A component is the unit that has parameters, defaults, a setter restatement and a coefficient block.
-enum Comp : uint8_t { CP_PLATE, CP_CHORUS, CP_PITCH, CP_VOICE, CP_RACK, CP_SAMPLE, CP_ORDER, CP_COUNT };
+enum Comp : uint8_t { CP_PLATE, CP_CHORUS, CP_PITCH, CP_VOICE, CP_RACK, CP_SAMPLE, CP_ORDER, CP_METER, CP_COUNT };
 // The engine's coefficient arrays (olfx_engine.cpp gives each its pointer and stride).
-enum Dst : uint8_t { TO_DT, TO_CH, TO_PS, TO_VC, TO_FR, TO_SM, TO_ORD, TO_COUNT };
+enum Dst : uint8_t { TO_DT, TO_CH, TO_PS, TO_VC, TO_FR, TO_SM, TO_ORD, TO_MT, TO_COUNT };
 // A component of a kind: where its parameters start in the kind's fields, where its coefficients go.
 struct Part { Comp comp; uint8_t field0; Dst dst; };
 constexpr uint32_t kNoField = 0xFFFFFFFFu;
@@ -47,6 +47,8 @@ struct KindDesc {
     bool planes_32bit = false;                   // the kernel addresses the audio planes with 32-bit offsets
     bool pad_plate = false;                      // the plate runs n rounded up to 64 instances
     bool state_counts_padding = false;           // ... and state_bytes counts them (the chain's figure does not)
+    bool no_controls = false;                    // no control maps to the kind: olfx_control_map and olfx_control refuse it
+    bool reset_keeps_params = false;             // the parameters are configuration: olfx_reset clears the state alone
 
     bool takes_note_events() const { return instances != EFFECTS; }
 };
@@ -78,6 +80,7 @@ void derive_chorus(const float *p, double sr, uint32_t *c);
 void derive_pitchshift(const float *p, double sr, uint32_t *c);
 void derive_fxrack(const float *p, float sr, uint32_t *c);
 void derive_voice(const float *p, bool configured, bool moog, float sr, uint32_t *c);
+void derive_meter(const float *p, float sr, uint32_t *c);
 
 // An instance's coefficient record: the words of each destination array (field-major on the
 // device, CoefScatterArgs), in record order.

@@ -369,6 +369,21 @@ struct MixArgs {
 };
 hipError_t launch_mix(const MixArgs &a, hipStream_t s);
 
+// ----------------------------------------------------------------------------------------------
+// Level meter (meter.hip): per signal, the running RMS of ol::core::Rms and the sandbox firmware's
+// peak-hold follower over n_frames frames of in.  out != null (envelope mode): out[p][f][i] = the rms
+// after frame f; out == null (summary mode): the state alone advances.
+// ----------------------------------------------------------------------------------------------
+struct MeterArgs {
+    const float *in;            // [planes][n_frames][n], planes `plane` floats apart
+    float *out;                 // the same shape, or null
+    float *state;               // [MTS_N][planes * n]
+    const float *coef;          // [MTC_N][n]
+    uint64_t plane;
+    uint32_t n, n_frames, planes;
+};
+hipError_t launch_meter(const MeterArgs &a, hipStream_t s);
+
 // host side: record a global error message (olfx_last_error(NULL))
 void internal_set_error(const char *msg);
 

@@ -173,6 +173,16 @@ constexpr uint32_t kDkOrderEmpty = 0xFFFFFFFFu;     // a kit with an empty map: 
 enum { DKC_ORDER = 0, DKC_N };
 
 // ----------------------------------------------------------------------------------------------
+// Level meter (meter.hip): ol::core::Rms (corelib/ol_corelib.h:61-85) and the sandbox firmware's peak-hold
+// follower (ol_daisy/workouts/sandbox/main.cpp:98-137) per signal; a signal is one channel plane of one
+// instance.  State rows [MTS_N][planes * n], signal (plane p, instance i) at p * n + i; coefficients
+// [MTC_N][n], shared by an instance's channels: the window Rms::Init resolved, and the hold count.
+// ----------------------------------------------------------------------------------------------
+enum { MTS_SUM = 0, MTS_COUNT, MTS_RMS, MTS_PEAK, MTS_PEAK_COUNT, MTS_N };
+enum { MTC_WINDOW = 0, MTC_HOLD, MTC_N };
+inline bool is_meter_kind(int k) { return k == OLFX_KIND_METER || k == OLFX_KIND_METER_MONO; }
+
+// ----------------------------------------------------------------------------------------------
 // Effect rack ol::fx::FxRack<2> (fxrack.hip): delay lines + two Svf (channel 0) + ReverbSc stub.
 // ----------------------------------------------------------------------------------------------
 constexpr uint32_t kFrMaxDelay = 48000;     // MAX_DELAY (modules/fxlib/Fx.h:23): ring positions

@@ -34,6 +34,8 @@ KIND_NAMES = {
     "synth": _lib.KIND_SYNTH,
     "synth_svf": _lib.KIND_SYNTH_SVF,
     "drumkit": _lib.KIND_DRUMKIT,
+    "meter": _lib.KIND_METER,
+    "meter_mono": _lib.KIND_METER_MONO,
 }
 
 # parameter field names, in C-ABI order
@@ -63,6 +65,9 @@ PARAMS[_lib.KIND_SYNTH_SVF] = PARAMS[_lib.KIND_SYNTH]
 # the drum kit: eight voice slots of the voice's fields ("v3_filter_cutoff"), then the rack's (OLFX_DK_*)
 PARAMS[_lib.KIND_DRUMKIT] = ([f"v{p}_{f}" for p in range(_lib.DK_MAX_VOICES) for f in PARAMS[_lib.KIND_VOICE]]
                              + ["rack_" + p for p in PARAMS[_lib.KIND_FXRACK]])
+# the level meters: Rms::Init's window (0: sample_rate / 375) and the firmware's peak_hold (OLFX_MT_*)
+PARAMS[_lib.KIND_METER] = ["window", "peak_hold"]
+PARAMS[_lib.KIND_METER_MONO] = PARAMS[_lib.KIND_METER]
 
 
 def kind_info(kind: int, sample_rate: float = 48000.0) -> _lib.KindInfo:
@@ -303,6 +308,39 @@ class Engine:
                                     ctypes.c_void_p(out.ctypes.data), int(n_frames), _lib.IO_HOST,
                                     ctypes.c_void_p(stream)), self._h)
         return out
+
+    # ---- level meters (OLFX_KIND_METER, OLFX_KIND_METER_MONO) ----
+    def meter(self, x, stream=None) -> None:
+        """Summary mode: the levels follow x ([in_ch][frames][n], torch CUDA tensor or numpy array) and nothing
+        is written per frame (olfx_process with out = NULL); read them with levels().  process(x) is the
+        envelope mode: it returns the running rms of every frame."""
+        ich = self.info.in_channels
+        n_frames = int(x.shape[1])
+        if _is_torch(x):
+            import torch
+            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            assert tuple(x.shape) == (ich, n_frames, self.n), (tuple(x.shape), (ich, n_frames, self.n))
+            if stream is None:
+                stream = torch.cuda.current_stream(x.device).cuda_stream
+            check(self.lib.olfx_process(self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(0), n_frames,
+                                        _lib.IO_DEVICE, ctypes.c_void_p(stream)), self._h)
+            return
+        xin = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        assert xin.shape == (ich, n_frames, self.n), (xin.shape, (ich, n_frames, self.n))
+        if stream is None:
+            stream = self.lib.olfx_stream(self._h)
+        check(self.lib.olfx_process(self._h, ctypes.c_void_p(xin.ctypes.data), ctypes.c_void_p(0), n_frames,
+                                    _lib.IO_HOST, ctypes.c_void_p(stream)), self._h)
+
+    def levels(self, first: int = 0, count: int = -1) -> dict:
+        """The meters' state of instances first..first+count after the engine's queued blocks: float32 arrays
+        [count][channels] under "rms", "peak", "sum", "count" and "peak_count" (olfx_meter_read)."""
+        count = self.n - first if count < 0 else int(count)
+        ch = self.info.in_channels
+        buf = np.empty((count, ch, 5), np.float32)
+        check(self.lib.olfx_meter_read(self._h, int(first), count, buf.ctypes.data_as(ctypes.POINTER(_lib.MeterLevel))),
+              self._h)
+        return {name: np.ascontiguousarray(buf[:, :, k]) for k, name in enumerate(("rms", "peak", "sum", "count", "peak_count"))}
 
     # ---- voice buses: the Polyvoice / VoiceMap sums (Polyvoice.h:28-33, VoiceMap.h:64-73) ----
     def mix_config(self, buses: Sequence[Sequence[int]]) -> None:

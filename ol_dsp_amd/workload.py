@@ -46,6 +46,9 @@ RANGES["synth"] = RANGES["voice"] + RANGES["fxrack"][:-1] + [1.0]
 RANGES["synth_svf"] = RANGES["voice"] + RANGES["fxrack"][:-1] + ["int2"]
 # the drum kit: eight voice slots, each pad with its own draw, then the rack's with the topology from {0, 1}
 RANGES["drumkit"] = 8 * RANGES["voice"] + RANGES["fxrack"][:-1] + ["int2"]
+# the level meters: the reference's own settings (Rms::Init's default window, the firmware's peak_hold)
+RANGES["meter"] = [0.0, 96000.0]
+RANGES["meter_mono"] = RANGES["meter"]
 
 
 def _splitmix64(z: np.ndarray) -> np.ndarray:
