@@ -376,6 +376,13 @@ typedef struct olfx_voice_event {
     uint8_t  pad;
     float    value;     /* SET_FREQUENCY: Hz (finite); else unused */
 } olfx_voice_event;
+/* A note event at a frame inside the block (olfx_timed_events): `frame` counts from the first frame of
+   the next olfx_process and is a multiple of 4, the engine's frame granularity (the firmware's
+   AUDIO_BLOCK_SIZE, a MidiBuffer position rounded to it). */
+typedef struct olfx_timed_event {
+    uint32_t frame;         /* multiple of 4, below 2^31 */
+    olfx_voice_event ev;
+} olfx_timed_event;
 
 /* ---- control changes (MIDI CC / hardware controls; corelib/cc_map.h numbers) ----
    The reference's UpdateMidiControl(control, 0..127) / UpdateHardwareControl(control, float)
@@ -512,6 +519,20 @@ int olfx_control(olfx_engine *e, const olfx_control_event *ev, uint32_t n);
 int olfx_note_events(olfx_engine *e, const olfx_event *ev, uint32_t n);
 /* The same queue with SET_FREQUENCY (Voice::SetFrequency, SynthVoice.h:264-267) as well. */
 int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n);
+/* Note events at a frame inside the block (OLFX_KIND_VOICE, OLFX_KIND_VOICE_MOOG, OLFX_KIND_VOICE_SAMPLE).
+   Events apply in order of (frame, queueing order): olfx_note_events and olfx_voice_events queue at
+   frame 0, ties keep call order, and the events of one frame on one voice compose as a block's do.  One
+   olfx_process(N) computes, bit for bit, what a process call per distinct event frame below N computes
+   with that frame's events queued by olfx_voice_events before it -- output and state.  An event at or
+   past N stays queued with its frame reduced by N when the call returns (frame == N: frame 0 of the next
+   call), so a whole score can be queued up front and rendered block by block.  Parameter changes,
+   olfx_control, olfx_update, olfx_sample_voices and olfx_sample_bank still land at the block boundary,
+   before frame 0's events; olfx_reset drops pending timed events with the untimed ones.
+   OLFX_E_ARG (nothing is queued): a frame that is no multiple of 4 or not below 2^31, or a record
+   olfx_voice_events refuses.  OLFX_E_KIND: the synth kinds and the drum kit -- their Playing() and their
+   Polyvoice / VoiceMap routing change at the call, so which voice a later-framed note reaches would depend
+   on calls not yet made; timed routing needs a decision of its own.  OLFX_E_STATE: effect and meter kinds. */
+int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n);
 /* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF / OLFX_KIND_DRUMKIT: Playing() of the `voices` voices of instrument (kit) inst,
    as of the calls made so far. */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);

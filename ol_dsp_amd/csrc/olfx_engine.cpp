@@ -349,10 +349,11 @@ ChorusArgs chorus_args(const olfx_engine *e, uint32_t n_frames, uint64_t plane) 
 // coefficients are scattered on `s` ahead of the block's kernel; the voice kernel reads its events
 // itself.  A slot is rewritten only after the kernels that read it are done (its `consumed` event,
 // recorded by the caller after them: *used_slot).
-int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Slot **used_slot) {
+// `span`: the frames of the launch the packet is for (timed events below it become its segments).
+int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Slot **used_slot, uint32_t span) {
     *used_slot = nullptr;
     host::Shadow &hs = e->hs;
-    const bool evs = host::takes_note_events(e->kind) && !hs.events.empty();
+    const bool evs = host::takes_note_events(e->kind) && hs.has_events(span);
     const size_t m = hs.dirty_list.size(), m2 = hs.vdirty_list.size();    // (m2: a kit kind's voice slots)
     if (!m && !m2 && !evs) return OLFX_OK;
     using clk = std::chrono::steady_clock;
@@ -364,7 +365,7 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
         t_prev = t;
     };
     e->tr_calls++;
-    if (evs) hs.fold_events();
+    if (evs) hs.fold_segments(span);
     lap(0);
     CoefScatterArgs ca{};
     const uint32_t W = coef_segments(e, &ca);
@@ -432,7 +433,12 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     }
     if (evs) {
         va->ev = reinterpret_cast<const uint2 *>(dev + pl.o_ev);
-        va->ev_more = va->ev + (size_t)((hs.n_ev() + 63u) / 64u) * kVevCap;
+        va->ev_more = va->ev + pl.n_seg * (size_t)((hs.n_ev() + 63u) / 64u) * kVevCap;
+        if (pl.n_seg > 1) {               // timed events: the segmented kernel
+            va->n_seg = (uint32_t)pl.n_seg;
+            va->n_chunks = hs.n_chunks(span, kVoiceChunk);
+            va->seg = dev + pl.o_seg;
+        }
     }
     lap(5);
     return OLFX_OK;
@@ -610,6 +616,9 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.smp = e->sm_asg;
         a.bank = e->sm_bank;
         a.bank_bytes = (uint32_t)e->sm_bank_bytes;
+        a.n_seg = ev.n_seg;
+        a.n_chunks = ev.n_chunks;
+        a.seg = ev.seg;
         r = e->kind == OLFX_KIND_VOICE_SAMPLE ? launch_sampler(a, s) : launch_voice(a, s);
         break;
     }
@@ -890,7 +899,7 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     // slots allocated now, so that no block -- an all-voices note-off in the middle of a stream,
     // say -- pays a pinned / device allocation: the small ones at the copy threshold, the big ones
     // for the largest packet this engine can produce (up to 256 MiB each; larger on first need)
-    const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev());
+    const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev(), host::max_segments(kind));
     for (olfx_engine::Slot &sl : e->slot)
         if (!rc) rc = grow_slot(e, sl, olfx_engine::kCopyBytes / 4, false);
     if (maxw * 4 >= e->copy_bytes && maxw * 4 <= ((size_t)256 << 20))
@@ -982,6 +991,10 @@ int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n) {
     return e ? e->report(e->hs.voice_events(ev, n)) : OLFX_E_ARG;
 }
 
+int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n) {
+    return e ? e->report(e->hs.timed_events(ev, n)) : OLFX_E_ARG;
+}
+
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing) {
     return e ? e->report(e->hs.synth_playing(inst, playing)) : OLFX_E_ARG;
 }
@@ -1011,29 +1024,35 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
         if (rc) return rc;
     }
     // the block's parameter changes and note events: asynchronous, O(changed)
-    VoiceArgs ev{};
-    olfx_engine::Slot *sl = nullptr;
-    rc = submit_control(e, s, &ev, &sl);
-    if (rc) return rc;
-    if (io_flags == OLFX_IO_HOST) {
-        hipError_t r = hipSuccess;
-        if (fin) {
+    // One pass over all the frames -- unless timed events sit at more distinct frames than a launch takes
+    // segments (host::Shadow::span: the voice kinds, one output plane and no input): then a pass per run of
+    // segments, each with its own packet, the state carrying between them as between run_frames' tiles.
+    const bool host_io = io_flags == OLFX_IO_HOST;
+    const float *const rin = host_io ? (fin ? e->d_in : nullptr) : in;
+    float *const rout = host_io ? (summary ? nullptr : e->d_out) : out;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        const uint32_t span = e->hs.span(n_frames - f0);
+        VoiceArgs ev{};
+        olfx_engine::Slot *sl = nullptr;
+        rc = submit_control(e, s, &ev, &sl, span);
+        if (rc) return rc;
+        if (host_io && fin && f0 == 0) {
             std::memcpy(e->h_in, in, fin * 4);
-            r = hipMemcpyAsync(e->d_in, e->h_in, fin * 4, hipMemcpyHostToDevice, s);
+            const hipError_t r = hipMemcpyAsync(e->d_in, e->h_in, fin * 4, hipMemcpyHostToDevice, s);
+            if (r != hipSuccess) rc = e->hip_fail(r, "olfx_process: input copy");
         }
-        rc = r == hipSuccess ? run_frames(e, fin ? e->d_in : nullptr, summary ? nullptr : e->d_out, n_frames, s, ev)
-                             : e->hip_fail(r, "olfx_process: input copy");
-    } else {
-        rc = run_frames(e, in, out, n_frames, s, ev);
+        if (!rc) rc = run_frames(e, rin, rout ? rout + (size_t)f0 * e->n : nullptr, span, s, ev);
+        launched_on(e, s);
+        // the slot is free again once whatever was queued on `s` (the scatter, the kernels) is done --
+        // recorded on the error paths too, so a later block never overwrites a packet still being read
+        if (sl) {
+            const hipError_t r = slot_queued(e, sl, s);
+            if (!rc && r != hipSuccess) rc = e->hip_fail(r, "hipEventRecord(consumed)");
+        }
+        if (rc) return rc;
+        e->hs.advance(span);              // pending timed events count from the next launch
+        f0 += span;
     }
-    launched_on(e, s);
-    // the slot is free again once whatever was queued on `s` (the scatter, the kernels) is done --
-    // recorded on the error paths too, so a later block never overwrites a packet still being read
-    if (sl) {
-        const hipError_t r = slot_queued(e, sl, s);
-        if (!rc && r != hipSuccess) rc = e->hip_fail(r, "hipEventRecord(consumed)");
-    }
-    if (rc) return rc;
     if (io_flags == OLFX_IO_HOST) {
         if (fout) HIPCHK(e, hipMemcpyAsync(e->h_out, e->d_out, fout * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(e, hipStreamSynchronize(s));

@@ -516,6 +516,7 @@ uint32_t n_params_of(int kind) { return kind_desc(kind).n_params; }
 uint32_t in_channels(int kind) { return kind_desc(kind).in_ch; }
 uint32_t out_channels(int kind) { return kind_desc(kind).out_ch; }
 bool takes_note_events(int kind) { return kind_desc(kind).takes_note_events(); }
+uint32_t max_segments(int kind) { return kind_desc(kind).instances == KindDesc::VOICES ? kSegCap : 1u; }
 double algorithmic_bytes_per_frame(int kind) { return kind_desc(kind).bytes_per_frame; }
 double algorithmic_read_bytes_per_frame(int kind) { return kind_desc(kind).read_bytes_per_frame; }
 
@@ -631,6 +632,7 @@ void Shadow::reset() {
     n_components = 0;
     pre_changed = true;
     events.clear();
+    timed.clear();
     ev_slot.assign(n_ev(), -1);
     playing.assign((size_t)voices * n, 0);
     dirty_list.clear();
@@ -1072,6 +1074,62 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
     return OLFX_OK;
 }
 
+int Shadow::timed_events(const olfx_timed_event *ev, uint32_t count) {
+    if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_timed_events: not a voice engine");
+    // Playing() and the Polyvoice / VoiceMap routing change at the call: which voice a later-framed note
+    // reaches would depend on calls not yet made
+    if (instruments()) return fail(OLFX_E_KIND, "olfx_timed_events: the synth kinds and the drum kit route notes at the call");
+    if (count && !ev) return fail(OLFX_E_ARG, "olfx_timed_events: null events");
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_voice_event &v = ev[k].ev;
+        if ((ev[k].frame & 3u) || ev[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_events: event %u: frame %u (a multiple of 4 below 2^31)", k, ev[k].frame);
+        if (v.inst >= n || v.note > 127 || v.type > OLFX_EV_SET_FREQUENCY ||
+            (v.type == OLFX_EV_SET_FREQUENCY && !std::isfinite(v.value)))
+            return fail(OLFX_E_ARG, "olfx_timed_events: bad event %u", k);
+    }
+    // frame 0 is the untimed queue (one order of arrival for both calls); the rest merge into the pending
+    // list behind the queued events of their frame: both steps keep call order among ties
+    const size_t old = timed.size();
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ev[k].frame == 0u) events.push_back(ev[k].ev);
+        else timed.push_back(ev[k]);
+    }
+    const auto by_frame = [](const olfx_timed_event &x, const olfx_timed_event &y) { return x.frame < y.frame; };
+    std::stable_sort(timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
+    std::inplace_merge(timed.begin(), timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
+    return OLFX_OK;
+}
+
+uint32_t Shadow::span(uint32_t n_frames) const {
+    uint32_t segs = 1, last = 0;                          // segment 0 starts at frame 0, events or none
+    for (const olfx_timed_event &t : timed) {
+        if (t.frame >= n_frames) break;
+        if (t.frame != last) {
+            if (segs == kSegCap) return t.frame;
+            ++segs;
+            last = t.frame;
+        }
+    }
+    return n_frames;
+}
+
+void Shadow::advance(uint32_t span_) {
+    size_t k = 0;
+    for (olfx_timed_event &t : timed) {
+        t.frame = t.frame > span_ ? t.frame - span_ : 0u;
+        if (!t.frame) events.push_back(t.ev), ++k;        // (ahead of anything queued from now on)
+    }
+    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+}
+
+uint32_t Shadow::n_chunks(uint32_t span_, uint32_t chunk) const {
+    uint32_t c = 0;
+    for (size_t s = 0; s < seg_frame.size(); ++s)
+        c += ((s + 1 < seg_frame.size() ? seg_frame[s + 1] : span_) - seg_frame[s] + chunk - 1) / chunk;
+    return c;
+}
+
 // ol::synth::Polyvoice's calls on instrument `inst` (Polyvoice.h:35-77) as events of its voices (voice
 // slot p * npad + inst).  Playing() changes here, at the call, as SynthVoice's does (SynthVoice.h:
 // 245-260: NoteOn stores the note, NoteOff stores 0).  The reference's quirks follow from the same
@@ -1196,9 +1254,38 @@ float mtof_note(uint8_t note) {
 // GateOn = Seek(0) + Play() and GateOff = Pause() (SampleSoundSource.h:21-26): any NoteOn / GateOn of
 // the block seeks to 0 (VEV_SEEK), and `playing` follows the last gate call like the gate itself.
 void Shadow::fold_events() {
-    const uint32_t seek = kd->has_sample ? (uint32_t)VEV_SEEK : 0u;
     folded.clear();
-    for (const olfx_voice_event &ev : events) {
+    ev_count.clear();
+    ev_more.clear();
+    n_more = 0;
+    seg_frame.assign(1, 0u);
+    seg_first.assign(1, 0u);
+    fold_one(events.data(), events.size(), sizeof(olfx_voice_event));
+    events.clear();
+    seg_first.push_back((uint32_t)folded.size());
+}
+
+// Timed events: every segment folds on its own, as the queue of a block that started at its frame would.
+void Shadow::fold_segments(uint32_t span_) {
+    fold_events();                                        // segment 0: the frame-0 queue
+    size_t k = 0;
+    while (k < timed.size() && timed[k].frame < span_) {
+        size_t k1 = k;
+        while (k1 < timed.size() && timed[k1].frame == timed[k].frame) ++k1;
+        seg_frame.push_back(timed[k].frame);
+        fold_one(&timed[k].ev, k1 - k, sizeof(olfx_timed_event));
+        seg_first.push_back((uint32_t)folded.size());
+        k = k1;
+    }
+    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+}
+
+// `count` events `stride` bytes apart
+void Shadow::fold_one(const olfx_voice_event *evs, size_t count, size_t stride) {
+    const uint32_t seek = kd->has_sample ? (uint32_t)VEV_SEEK : 0u;
+    const size_t first = folded.size();
+    for (size_t e = 0; e < count; ++e) {
+        const olfx_voice_event &ev = *reinterpret_cast<const olfx_voice_event *>(reinterpret_cast<const char *>(evs) + e * stride);
         int32_t &k = ev_slot[ev.inst];
         if (k < 0) {
             k = (int32_t)folded.size();
@@ -1220,18 +1307,17 @@ void Shadow::fold_events() {
         default: r.op = (r.op | VEV_GATE_SET) & ~VEV_GATE_ON; break;   // NoteOff / GateOff
         }
     }
-    events.clear();
     // records per workgroup (64 voices); crowded workgroups (more than kVevCap records) get a run
     // of the overflow list each, in group order
     const uint32_t groups = (n_ev() + 63u) / 64u;
-    ev_count.assign(groups, 0u);
-    for (const Folded &r : folded) {
-        ev_count[r.inst >> 6]++;
-        ev_slot[r.inst] = -1;
+    const size_t g0 = ev_count.size();                    // this segment's groups
+    ev_count.resize(g0 + groups, 0u);
+    for (size_t r = first; r < folded.size(); ++r) {
+        ev_count[g0 + (folded[r].inst >> 6)]++;
+        ev_slot[folded[r].inst] = -1;
     }
-    ev_more.assign(groups, 0u);
-    n_more = 0;
-    for (uint32_t g = 0; g < groups; ++g)
+    ev_more.resize(g0 + groups, 0u);
+    for (size_t g = g0; g < g0 + groups; ++g)
         if (ev_count[g] > kVevCap) {
             ev_more[g] = n_more;
             n_more += ev_count[g];
@@ -1239,27 +1325,37 @@ void Shadow::fold_events() {
 }
 
 // The folded records into a packet's event section (VoiceArgs::ev layout, olfx_internal.h):
-// `fix` = [groups][kVevCap] 8-B slots, then the overflow list.
+// `fix` = [groups][kVevCap] 8-B slots, then the overflow list.  Segments (fold_segments): the slots of every
+// segment, [n_seg][groups][kVevCap], one overflow list, and -- two segments or more -- their start frames.
 void Shadow::write_events(uint32_t *fix) {
-    const uint32_t groups = (n_ev() + 63u) / 64u;
-    std::memset(fix, 0, (size_t)groups * kVevCap * 8);
-    uint32_t *more = fix + (size_t)groups * kVevCap * 2;
+    const size_t groups = ev_count.size();                // every segment's
+    std::memset(fix, 0, groups * kVevCap * 8);
+    uint32_t *more = fix + groups * kVevCap * 2;
     ev_fill.assign(groups, 0u);
-    for (const Folded &r : folded) {
-        const uint32_t g = r.inst >> 6;
-        const uint32_t k = ev_fill[g]++;
-        uint32_t *rec = ev_count[g] <= kVevCap ? fix + 2 * ((size_t)g * kVevCap + k) : more + 2 * ((size_t)ev_more[g] + k);
-        rec[0] = (r.inst & 63u) | r.op << 8;
-        rec[1] = r.freq;
-    }
-    for (uint32_t g = 0; g < groups; ++g)
-        if (ev_count[g] > kVevCap) {
-            fix[2 * (size_t)g * kVevCap] = VEV_MORE << 8 | ev_count[g] << 16;
-            fix[2 * (size_t)g * kVevCap + 1] = ev_more[g];
+    const size_t per_seg = (n_ev() + 63u) / 64u;
+    for (size_t sgm = 0; sgm + 1 < seg_first.size(); ++sgm)
+        for (size_t f = seg_first[sgm]; f < seg_first[sgm + 1]; ++f) {
+            const Folded &r = folded[f];
+            const size_t g = sgm * per_seg + (r.inst >> 6);
+            const uint32_t k = ev_fill[g]++;
+            uint32_t *rec = ev_count[g] <= kVevCap ? fix + 2 * (g * kVevCap + k) : more + 2 * ((size_t)ev_more[g] + k);
+            rec[0] = (r.inst & 63u) | r.op << 8;
+            rec[1] = r.freq;
         }
+    for (size_t g = 0; g < groups; ++g)
+        if (ev_count[g] > kVevCap) {
+            fix[2 * g * kVevCap] = VEV_MORE << 8 | ev_count[g] << 16;
+            fix[2 * g * kVevCap + 1] = ev_more[g];
+        }
+    if (seg_frame.size() > 1) {
+        uint32_t *tab = more + 2 * (size_t)n_more;
+        for (size_t sgm = 0; sgm < seg_frame.size(); ++sgm) tab[sgm] = seg_frame[sgm];
+        if (seg_frame.size() & 1u) tab[seg_frame.size()] = 0u;       // the section is whole 8-B records
+    }
 }
 
-PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev, size_t m2, uint32_t W2) {
+PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev, size_t m2, uint32_t W2,
+                       uint32_t n_seg) {
     PacketPlan pl;
     pl.dense = m == n;                                   // every instance: no instance list
     pl.o_inst = 0;
@@ -1271,13 +1367,20 @@ PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_mo
         pl.o_val2 = pl.o_inst2 + up4(m2);
         pl.o_ev = up4(pl.o_val2 + (size_t)W2 * m2);
     }
-    pl.words = pl.o_ev + (evs ? 2 * ((size_t)(((n_ev ? n_ev : n) + 63u) / 64u) * kVevCap + n_more) : 0);
+    pl.n_seg = n_seg ? n_seg : 1u;
+    pl.words = pl.o_ev + (evs ? 2 * (pl.n_seg * (size_t)(((n_ev ? n_ev : n) + 63u) / 64u) * kVevCap + n_more) : 0);
+    if (evs && pl.n_seg > 1) {                            // the segments' start frames
+        pl.o_seg = pl.words;
+        pl.words += (pl.n_seg + 1u) & ~(size_t)1u;
+    }
     return pl;
 }
 
-size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev) {
+size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev, uint32_t n_seg) {
     const size_t n = n_inst, W = coef_segments(kind).total(), nv = n_ev ? n_ev : n_inst;
-    const size_t ev = takes_note_events(kind) ? 2 * ((nv + 63) / 64 * kVevCap + nv) : 0;
+    // (timed events: a launch's segments and their start frames)
+    const size_t segs = n_seg ? n_seg : 1;
+    const size_t ev = takes_note_events(kind) ? 2 * segs * ((nv + 63) / 64 * kVevCap + nv) + (segs > 1 ? segs : 0) : 0;
     // a kit kind: every voice slot's list entry and record as well (n_ev = voices x n rounded up to 64)
     const KindDesc &kd = kind_desc(kind);
     const size_t nslots = kd.voice_slots ? nv / ((n + 63) / 64 * 64) * n : 0;

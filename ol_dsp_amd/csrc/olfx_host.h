@@ -93,22 +93,29 @@ Segments voice_segments(int kind);           // a kit kind's record per voice sl
 
 // ---- the control packet (u32 words, 16-B aligned sections) ----
 // instance list (absent when every instance changed: dense) | coefficient records [W][m] | event
-// slots [groups][kVevCap] and the overflow list, 8-B records (write_events)
+// slots [groups][kVevCap] and the overflow list, 8-B records (write_events); with timed events, n_seg >= 2
+// segments: slots [n_seg][groups][kVevCap] | one overflow list | the segments' start frames [n_seg]
+// (olfx_layout.h kSegCap)
 struct PacketPlan {
     bool dense;
     size_t o_inst, o_val, o_ev, words;
+    size_t n_seg = 1, o_seg = 0;          // o_seg: the start frames (n_seg >= 2)
     // a kit kind's second section, ahead of the events: the m2 changed voice slots (device slots p * npad + kit,
     // always listed) and their records [W2][m2]
     size_t m2 = 0, o_inst2 = 0, o_val2 = 0;
 };
 // n instances of which m changed, W words per record, `evs`: an event section with n_more
 // overflow records for n_ev voice slots (0: the n instances are the voices)
+// n_seg: the event section's segments (timed events)
 PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0, size_t m2 = 0,
-                       uint32_t W2 = 0);
+                       uint32_t W2 = 0, uint32_t n_seg = 1);
 // The largest packet an engine can produce: every instance's coefficients and, for voices, an
 // event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).  A kit
-// kind: every kit's record, every voice slot's record and an event per voice.
-size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0);
+// kind: every kit's record, every voice slot's record and an event per voice.  n_seg: the segments of a
+// launch (timed events: the voice kinds' kSegCap, max_segments) -- an event for every voice in each.
+size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0, uint32_t n_seg = 1);
+// the segments one launch of a kind can take: kSegCap for the kinds olfx_timed_events accepts, else 1
+uint32_t max_segments(int kind);
 
 struct Folded { uint32_t inst, op, freq, pad; };
 
@@ -174,11 +181,18 @@ struct Shadow {
     std::vector<uint8_t> note2voice, chan2voice;
     int64_t n_components = 0;             // rack instances with OLFX_FR_TOPOLOGY >= 2
     bool pre_changed = true;              // a reverb pre-delay changed since the flag was last cleared
-    std::vector<olfx_voice_event> events; // queued for the next block
-    std::vector<Folded> folded;           // fold_events: one record per voice, by first appearance
-    // per workgroup: records, first overflow record (crowded groups), records written so far
+    std::vector<olfx_voice_event> events; // queued for the next block (its frame 0)
+    // olfx_timed_events: the events past frame 0, stably ordered by frame (frames count from the next block's
+    // first frame; an event at frame 0 goes to `events`, which keeps the queueing order across both calls)
+    std::vector<olfx_timed_event> timed;
+    // fold_events / fold_segments: one record per voice and segment, segment by segment and by first
+    // appearance; segment s is folded[seg_first[s] .. seg_first[s + 1]) and starts at frame seg_frame[s]
+    std::vector<Folded> folded;
+    std::vector<uint32_t> seg_frame, seg_first;
+    // per segment and workgroup ([n_seg][groups]): records, first overflow record (crowded groups), records
+    // written so far
     std::vector<uint32_t> ev_count, ev_more, ev_fill;
-    uint32_t n_more = 0;                  // overflow records
+    uint32_t n_more = 0;                  // overflow records, all segments
     std::vector<int32_t> ev_slot;         // voice -> its record in `folded` during fold_events, else -1
     std::vector<uint32_t> h_words;        // scratch for a record
     // sample voices: the bank in use and every voice's Sample.  Configuration like the voice buses:
@@ -223,6 +237,16 @@ struct Shadow {
     int control(const olfx_control_event *ev, uint32_t count);       // rack topology routing included
     int note_events(const olfx_event *ev, uint32_t count);
     int voice_events(const olfx_voice_event *ev, uint32_t count);
+    int timed_events(const olfx_timed_event *ev, uint32_t count);
+    // The frames of the next launch of a block of n_frames: all of them, unless more than kSegCap distinct
+    // event times lie in it (frame 0 included, with or without events) -- then up to the first time that
+    // does not fit.
+    uint32_t span(uint32_t n_frames) const;
+    // whether a launch of `span` frames has events
+    bool has_events(uint32_t span_) const { return !events.empty() || (!timed.empty() && timed.front().frame < span_); }
+    // After a launch of `span` frames: the pending events' frames count from the next launch (an event at
+    // frame `span` is at its frame 0).  fold_segments(span) has taken the events below `span`.
+    void advance(uint32_t span_);
     int synth_playing(uint32_t inst, uint8_t *out);                  // [voices]
     // olfx_drumkit_map: VoiceMap::SetVoice records in order, judged on the state after the last
     int drumkit_map(const olfx_drumkit_voice *recs, uint32_t count);
@@ -244,8 +268,15 @@ struct Shadow {
     void derive_record(uint32_t i, uint32_t *w) const;
     // The queued events as one record per voice (`folded`) and their place in the event section.
     void fold_events();
+    // The same for a launch of `span` frames: segment 0 is the frame-0 queue (it may be empty), then one
+    // segment per distinct frame of the timed events below `span`, which leave the pending list.
+    void fold_segments(uint32_t span_);
+    uint32_t n_seg() const { return (uint32_t)seg_frame.size(); }
+    // the launch's chunks (VoiceArgs::n_chunks): each segment's frames in chunks of `chunk`
+    uint32_t n_chunks(uint32_t span_, uint32_t chunk) const;
     PacketPlan plan(bool evs) const {
-        return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords);
+        return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords,
+                           evs ? n_seg() : 1u);
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
@@ -269,6 +300,8 @@ private:
     void route_kit(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // the synth's Polyvoice router (Polyvoice.h:35-77): one instrument event -> per-voice events
     void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
+    // one segment's events onto `folded`, ev_count and ev_more
+    void fold_one(const olfx_voice_event *ev, size_t count, size_t stride);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
         return kd->instances == KindDesc::VOICES || (n_fields && field0 < kd->voice_end && field0 + n_fields > kd->voice0);

@@ -232,6 +232,12 @@ struct VoiceArgs {
     const uint32_t *smp;        // [SMC_N][n]
     const float *bank;          // bank_bytes bytes (nullptr / 0: no bank -- every SMC_LEN is 0 then)
     uint32_t bank_bytes;
+    // timed events (olfx_layout.h kSegCap): n_seg >= 2 segments, segment s starting at frame seg[s]
+    // (seg[0] = 0, ascending, multiples of 4 below n_frames) with the fixed slots ev[s n_groups kVevCap ..];
+    // n_chunks: the launch's chunks, each segment's frames in chunks of its own (sum of ceil(L / kVcChunk)).
+    // n_seg <= 1: one segment, the launch as it was
+    uint32_t n_seg, n_chunks;
+    const uint32_t *seg;
 };
 
 // Coefficient records of the instances whose parameters changed (olfx_engine.cpp submit_control):

@@ -139,6 +139,17 @@ enum : uint32_t {
 // kVevCap records puts them all in the overflow list and marks slot 0:
 // x = VEV_MORE << 8 | count << 16, y = first record in ev_more (a second round trip, for it only).
 constexpr uint32_t kVevCap = 4;
+// Timed events (olfx_timed_events): a launch's frames are up to kSegCap segments, each with fixed slots of
+// its own -- [segments][groups][kVevCap], then one overflow list for all of them (a crowded slot 0's y
+// counts from its start), then the segments' start frames (u32 each).  One segment is the layout above.
+// 16: every quad of a 64-frame block, or the firmware's MIDI rate over a 64-frame host block, in one
+// launch; the kernel stages all of a launch's records up front (16 fixed-slot reads in flight over the
+// host link, 32 VGPRs before the envelopes are live) into 8 KB of LDS per workgroup, which leaves two
+// workgroups per CU to the sample voice (54 KB + 8) as to the others.  A block with more distinct times
+// runs as several launches (olfx_engine.cpp), and the worst packet stays kSegCap records per voice.
+constexpr uint32_t kSegCap = 16;
+// frames per chunk of the voice kernels (voice_roles.h kVcChunk): a segment's frames run in chunks of its own
+constexpr uint32_t kVoiceChunk = 8;
 
 // ----------------------------------------------------------------------------------------------
 // Sample voices (sampler.hip): SynthVoice(SampleSoundSource<1>(Sample), SvfFilter).  The voice's

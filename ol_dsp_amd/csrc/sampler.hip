@@ -58,21 +58,33 @@ __device__ __forceinline__ float bank_load(__amdgpu_buffer_rsrc_t bank, uint32_t
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void sampler_block_v1(VoiceArgs a) {
+// SEG (sampler_block_v1_seg, timed events: voice_roles.h VoiceSegs): the block is its segments' chunks.  SRC
+// takes a segment's VEV_SEEK and `playing` at that segment's first chunk, where a window starts too (a window
+// lies inside one segment: at most 8 chunks, all full but the segment's last), and stores the last
+// frequency at the end.  The ring is addressed by chunk, 8 rows each whatever the chunk's frames: that is the
+// frame while the chunks are full, and keeps a short chunk's successor off FILT's rows.
+template <bool SEG>
+__device__ __forceinline__ void sampler_v1(const VoiceArgs &a) {
     __shared__ VoiceEnvQ eq;                    // ENV -> FREQ (fc_in), FILT (amp)
     __shared__ float win[kSmRows * kSmStride];  // SRC -> FILT: the source, [frame mod 128][voice], padded rows
     __shared__ VoiceFreqQ fdq;                  // FREQ -> FILT: (-damp, fq)
     __shared__ uint2 evslot[64];                // ENV's staging of the block's events (SRC reads it)
     __shared__ uint32_t hw_simd[5];
+    VoiceSegs *sg = nullptr;
+    if constexpr (SEG) {
+        __shared__ VoiceSegs segs;
+        sg = &segs;
+        voice_segs_bounds(a, segs);               // published by voice_role_of_wave's barrier
+    }
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // roles by SIMD, as v5: ENV with FILT, SRC (in OSC's place) with FREQ
     const uint32_t role = voice_role_of_wave(hw_simd, lane, wave);
     if (role == 3u) __builtin_amdgcn_s_setprio(2);
-    const VoiceLane v = voice_lane(a);
+    const VoiceLane v = SEG ? voice_lane_seg(a) : voice_lane(a);
 
     if (role == 0) {
-        voice_role_env(a, v, eq, evslot);
+        voice_role_env<SEG>(a, v, eq, evslot, sg);
     } else if (role == 1) {
         // ---- SRC: Sample::Process over the bank ----
         const uint32_t n = v.n, i = v.i, nf = v.nf, nsteps = v.nsteps;
@@ -101,9 +113,13 @@ __global__ __launch_bounds__(256) void sampler_block_v1(VoiceArgs a) {
         // that makes current_frame_ > loop_end_)
         [[maybe_unused]] const uint32_t limit = (loop && le) ? le : len;
         const uint32_t lane4 = lane * 4u;
+        // SEG: the frame the current window ends at; the last frequency a segment set
+        [[maybe_unused]] uint32_t wend = 0u, fbits = 0u;
+        [[maybe_unused]] bool fset = false;
+        SegCursor<SEG> cu(sg, a.n_seg);
 
         for (uint32_t k = 0; k < nsteps; ++k) {
-            if (k == 1) {
+            if (!SEG && k == 1) {
                 // the block's events, staged by ENV before the first barrier: any NoteOn / GateOn is
                 // Seek(0), the last gate call Play() or Pause() (SampleSoundSource.h:21-26); the pitch
                 // is stored (SynthVoice::freq_)
@@ -112,10 +128,25 @@ __global__ __launch_bounds__(256) void sampler_block_v1(VoiceArgs a) {
                 if (ev.op & VEV_GATE_SET) playing = (ev.op & VEV_GATE_ON) != 0u;
                 if (ev.op & VEV_FREQ) s[VCS_FREQ * n + i] = ev.freq;
             }
-            if (k >= 1 && k + 1 < nsteps && ((k - 1) & (kSmWin / kVcChunk - 1)) == 0) {
-                // window w = (k - 1) / 8: frames [f0, f0 + nwin)
+            if constexpr (SEG) {
+                if (k >= 1 && k + 1 < nsteps && cu.first) {
+                    const VoiceEv ev = seg_event(*sg, cu.seg, v.me);
+                    if (ev.op & VEV_SEEK) pos = 0u;
+                    if (ev.op & VEV_GATE_SET) playing = (ev.op & VEV_GATE_ON) != 0u;
+                    if (ev.op & VEV_FREQ) {
+                        fbits = __float_as_uint(ev.freq);
+                        fset = true;
+                    }
+                }
+            }
+            if (k >= 1 && k + 1 < nsteps &&
+                (SEG ? (cu.first || cu.f0 == wend) : ((k - 1) & (kSmWin / kVcChunk - 1)) == 0)) {
+                // window w = (k - 1) / 8: frames [f0, f0 + nwin) in ring rows f0 ... (SEG: the rows of chunk
+                // k - 1 ..., the frames left of the segment)
                 const uint32_t f0 = (k - 1) * kVcChunk;
-                const uint32_t nwin = nf - f0 < kSmWin ? nf - f0 : kSmWin;
+                const uint32_t left = SEG ? cu.end - cu.f0 : nf - f0;
+                const uint32_t nwin = left < kSmWin ? left : kSmWin;
+                if constexpr (SEG) wend = cu.f0 + nwin;
                 const bool silent = !playing || (pos >= len && (!loop || ls >= len));
 #ifdef OLFX_SAMPLER_PER_LANE
                 // variant build (tools/sampler_ab.py): every playing voice on the per-frame gather, i.e.
@@ -171,23 +202,34 @@ __global__ __launch_bounds__(256) void sampler_block_v1(VoiceArgs a) {
                     }
                 }
             }
+            if constexpr (SEG)
+                if (k >= 1 && k + 1 < nsteps) cu.next();
             __syncthreads();
         }
+        if constexpr (SEG)
+            if (fset) s[VCS_FREQ * n + i] = __uint_as_float(fbits);     // the last segment's
         s[VCS_SM_POS * n + i] = __uint_as_float(pos);
         s[VCS_SM_FLAGS * n + i] = __uint_as_float((mg & ~1u) | (playing ? 1u : 0u));
     } else if (role == 2) {
-        voice_role_freq(a, v, eq, fdq);
+        voice_role_freq<SEG>(a, v, eq, fdq, sg);
     } else {
         // chunk c's source samples: ring rows (8 c + j) mod 128, this lane's column
-        voice_role_filt<kSmStride>(a, v, eq, fdq, [&](uint32_t c2) {
+        voice_role_filt<kSmStride, SEG>(a, v, eq, fdq, [&](uint32_t c2) {
             return &win[((c2 * kVcChunk) & (kSmRows - 1)) * kSmStride + lane];
-        });
+        }, sg);
     }
 }
+__global__ __launch_bounds__(256) void sampler_block_v1(VoiceArgs a) { sampler_v1<false>(a); }
+__global__ __launch_bounds__(256) void sampler_block_v1_seg(VoiceArgs a) { sampler_v1<true>(a); }
 
 hipError_t launch_sampler(const VoiceArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
     if ((uint64_t)kVcChunk * a.n * 4u > 0xFFFFFFFFull) return hipErrorInvalidValue;   // FILT's chunk output resource
+    if (a.n_seg > 1) {                    // timed events: the segmented kernel
+        if (a.n_seg > kSegCap || !a.seg || !a.ev) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(sampler_block_v1_seg, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(sampler_block_v1, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
     return hipGetLastError();
 }

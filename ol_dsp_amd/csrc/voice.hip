@@ -30,11 +30,22 @@ namespace olfx {
 //   filter wave : LadderFilter::Process, output store
 // The ladder's serial recurrence dominates the voice, so the feed roles share one wave.  (The Svf
 // voice runs voice_block_v5 below, over four role waves.)
-__global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
+// SEG (voice_block_v4_seg, timed events: voice_roles.h VoiceSegs): the block is its segments' chunks; at a
+// segment's first chunk the feed wave applies that segment's events to its live registers -- the gate
+// events and Env::begin as at a launch's start, the segment's frequency -- and the state is stored once.
+template <bool SEG>
+__device__ __forceinline__ void voice_v4(const VoiceArgs &a) {
     constexpr uint32_t kRoles = 2u;
     __shared__ float4 q[2][kVcChunk][64];
     __shared__ uint32_t fflags[64];
     __shared__ uint2 evslot[64];
+    VoiceSegs *sg = nullptr;
+    if constexpr (SEG) {
+        __shared__ VoiceSegs segs;
+        sg = &segs;
+        voice_segs_bounds(a, segs);
+        __syncthreads();
+    }
     const uint32_t n = a.n;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -44,7 +55,7 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
     const uint32_t i = i0 < n ? i0 : n - 1;
     const uint32_t me = i - blockIdx.x * 64;
     const uint32_t nf = a.n_frames;
-    const uint32_t nchunks = (nf + kVcChunk - 1) / kVcChunk;
+    const uint32_t nchunks = SEG ? a.n_chunks : (nf + kVcChunk - 1) / kVcChunk;
     const float *c = a.coef;
     float *s = a.state;
     const bool filt_role = wave == kRoles - 1;
@@ -57,12 +68,18 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
         uint32_t flags0 = __float_as_uint(s[VCS_FLAGS * n + i]);
         float xa0 = s[VCS_ENVA_X * n + i], xf0 = s[VCS_ENVF_X * n + i];
         const float freq_s = s[VCS_FREQ * n + i];
-        const VoiceEv ev = voice_event(a, evslot, lane, me);
-        apply_gate_events(ev, flags0, xa0, xf0);
-        const bool gate = (flags0 >> 8) & 1u;
+        VoiceEv ev{0u, 0.0f};
+        if constexpr (SEG) {
+            voice_events_stage(a, *sg, lane, blockIdx.x);
+        } else {
+            ev = voice_event(a, evslot, lane, me);
+            apply_gate_events(ev, flags0, xa0, xf0);
+        }
+        bool gate = (flags0 >> 8) & 1u;
         const float amp_amt = c[VCC_AMP_AMT * n + i], port_c = c[VCC_PORT_COEF * n + i];
         const float inv_sr = c[VCC_INV_SR * n + i];
-        const float freq = (ev.op & VEV_FREQ) ? ev.freq : freq_s;
+        float freq = (ev.op & VEV_FREQ) ? ev.freq : freq_s;
+        [[maybe_unused]] bool fset = false;               // SEG: some segment set the frequency
         const float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
         // ladder: drive_scaled (VCC_DRIVE), 1/(4 sr) (VCC_FC_MAX)
         const float drive = c[VCC_DRIVE * n + i];
@@ -71,17 +88,48 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
         float port_z = s[VCS_PORT_Z * n + i];
         bool gprev_a = (flags0 >> 6) & 1u, gprev_f = (flags0 >> 7) & 1u;
         Env ea, ef;
-        if constexpr (AMP)
-            ea.begin(gate, gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * n + i],
-                     c[VCC_ATK_TGT_A * n + i], c[VCC_DEC_D0A * n + i], c[VCC_REL_D0A * n + i], c[VCC_SUS_A * n + i]);
-        if constexpr (CUT)
-            ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * n + i],
-                     c[VCC_ATK_TGT_F * n + i], c[VCC_DEC_D0F * n + i], c[VCC_REL_D0F * n + i], c[VCC_SUS_F * n + i]);
+        // (SEG: the envelope coefficients stay in registers for the segment starts)
+        [[maybe_unused]] float ca[5], cf[5];
+        if constexpr (SEG) {
+            ca[0] = c[VCC_ATK_D0A * n + i]; ca[1] = c[VCC_ATK_TGT_A * n + i]; ca[2] = c[VCC_DEC_D0A * n + i];
+            ca[3] = c[VCC_REL_D0A * n + i]; ca[4] = c[VCC_SUS_A * n + i];
+            cf[0] = c[VCC_ATK_D0F * n + i]; cf[1] = c[VCC_ATK_TGT_F * n + i]; cf[2] = c[VCC_DEC_D0F * n + i];
+            cf[3] = c[VCC_REL_D0F * n + i]; cf[4] = c[VCC_SUS_F * n + i];
+        } else {
+            if constexpr (AMP)
+                ea.begin(gate, gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * n + i],
+                         c[VCC_ATK_TGT_A * n + i], c[VCC_DEC_D0A * n + i], c[VCC_REL_D0A * n + i], c[VCC_SUS_A * n + i]);
+            if constexpr (CUT)
+                ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * n + i],
+                         c[VCC_ATK_TGT_F * n + i], c[VCC_DEC_D0F * n + i], c[VCC_REL_D0F * n + i], c[VCC_SUS_F * n + i]);
+        }
 
+        SegCursor<SEG> cu(sg, a.n_seg);
         for (uint32_t k = 0; k <= nchunks; ++k) {
             if (k < nchunks) {
+                if constexpr (SEG) {
+                    if (cu.first) {
+                        if (k) {                 // the live state as the flags word and levels a launch would load
+                            flags0 = ea.mode | ef.mode << 3 | (uint32_t)gprev_a << 6 | (uint32_t)gprev_f << 7 |
+                                     (uint32_t)gate << 8;
+                            xa0 = ea.x;
+                            xf0 = ef.x;
+                        }
+                        const VoiceEv sev = seg_event(*sg, cu.seg, me);
+                        apply_gate_events(sev, flags0, xa0, xf0);
+                        gate = (flags0 >> 8) & 1u;
+                        gprev_a = (flags0 >> 6) & 1u;
+                        gprev_f = (flags0 >> 7) & 1u;
+                        if (sev.op & VEV_FREQ) {
+                            freq = sev.freq;
+                            fset = true;
+                        }
+                        ea.begin(gate, gprev_a, flags0 & 7u, xa0, ca[0], ca[1], ca[2], ca[3], ca[4]);
+                        ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, cf[0], cf[1], cf[2], cf[3], cf[4]);
+                    }
+                }
                 const uint32_t f0 = k * kVcChunk;
-                const uint32_t m = nf - f0 < (uint32_t)kVcChunk ? nf - f0 : (uint32_t)kVcChunk;
+                const uint32_t m = SEG ? cu.len() : (nf - f0 < (uint32_t)kVcChunk ? nf - f0 : (uint32_t)kVcChunk);
                 float4 *qb = &q[k & 1][0][lane];
                 for_chunk(m, [&](uint32_t j) {
                     float2 ab, cd;
@@ -95,6 +143,7 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
                         reinterpret_cast<float2 *>(&qb[j * 64])[1] = cd;
                     }
                 });
+                cu.next();
             }
             __syncthreads();
         }
@@ -107,7 +156,7 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
             s[VCS_PORT_Z * n + i] = port_z;
             s[VCS_ENVA_X * n + i] = ea.x;
             s[VCS_FLAGS * n + i] = __uint_as_float(ea.mode | fbits | (uint32_t)gprev_a << 6 | (uint32_t)gate << 8);
-            if (ev.op & VEV_FREQ) s[VCS_FREQ * n + i] = freq;
+            if (SEG ? fset : (ev.op & VEV_FREQ) != 0u) s[VCS_FREQ * n + i] = freq;     // SEG: the last segment's
         }
         if constexpr (CUT) s[VCS_ENVF_X * n + i] = ef.x;
     };
@@ -124,16 +173,18 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
         }
         L.old = s[VCS_LOLD * n + i];
         float *out = a.out + i;
+        SegCursor<SEG> cu(sg, a.n_seg);
         for (uint32_t k = 0; k <= nchunks; ++k) {
             if (k > 0) {
-                const uint32_t f0 = (k - 1) * kVcChunk;
-                const uint32_t m = nf - f0 < (uint32_t)kVcChunk ? nf - f0 : (uint32_t)kVcChunk;
+                const uint32_t f0 = SEG ? (uint32_t)cu.f0 : (k - 1) * kVcChunk;
+                const uint32_t m = SEG ? cu.len() : (nf - f0 < (uint32_t)kVcChunk ? nf - f0 : (uint32_t)kVcChunk);
                 const float4 *qb = &q[(k - 1) & 1][0][lane];
                 for_chunk(m, [&](uint32_t j) {
                     const float4 v = qb[j * 64];
                     const float y = ladder_tick(L, v, k_or_unused);
                     out[(size_t)(f0 + j) * n] = y;
                 });
+                cu.next();
             }
             __syncthreads();
         }
@@ -146,6 +197,8 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
         s[VCS_LOLD * n + i] = L.old;
     }
 }
+__global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) { voice_v4<false>(a); }
+__global__ __launch_bounds__(128) void voice_block_v4_seg(VoiceArgs a) { voice_v4<true>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // voice_block_v5 (SvfFilter voices): v4's arithmetic, operation for operation, over
@@ -164,12 +217,21 @@ __global__ __launch_bounds__(128) void voice_block_v4(VoiceArgs a) {
 // ---------------------------------------------------------------------------------------------
 // FILT (the Svf recurrence, the critical chain of the ENV + FILT pair) issues ahead of ENV on
 // their SIMD at wave priority 2: ~2 % same-box; OSC raised too was slower.
-__global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
+// SEG (voice_block_v5_seg, timed events): as voice_block_v4_seg; ENV stages every segment's records, OSC
+// takes a segment's frequency at that segment's first chunk and stores the last one at the end.
+template <bool SEG>
+__device__ __forceinline__ void voice_v5(const VoiceArgs &a) {
     __shared__ VoiceEnvQ eq;                    // ENV -> OSC, FREQ (fc_in), FILT (amp): three chunks live
     __shared__ float sq[2][kVcChunk][64];       // OSC -> FILT: src
     __shared__ VoiceFreqQ fdq;                  // FREQ -> FILT: (-damp, fq)
     __shared__ uint2 evslot[64];                // ENV's staging of the block's events (OSC reads it)
     __shared__ uint32_t hw_simd[5];             // the SIMD of each wave; [4]: wave 0's slot parity
+    VoiceSegs *sg = nullptr;
+    if constexpr (SEG) {
+        __shared__ VoiceSegs segs;
+        sg = &segs;
+        voice_segs_bounds(a, segs);               // published by voice_role_of_wave's barrier
+    }
     const uint32_t n = a.n;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -177,14 +239,12 @@ __global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
     const uint32_t role = voice_role_of_wave(hw_simd, lane, wave);
     // the role with the per-sample recurrence (FILT) ahead of its SIMD partner at issue
     if (role == 3u) __builtin_amdgcn_s_setprio(2);
-    const VoiceLane v = voice_lane(a);           // dead lanes mirror voice n-1, as in v4
+    const VoiceLane v = SEG ? voice_lane_seg(a) : voice_lane(a);   // dead lanes mirror voice n-1, as in v4
     const uint32_t i = v.i, me = v.me, nsteps = v.nsteps;
     const float *c = a.coef;
     float *s = a.state;
-    auto len = [&](uint32_t k) { return v.len(k); };
-
     if (role == 0) {
-        voice_role_env(a, v, eq, evslot);
+        voice_role_env<SEG>(a, v, eq, evslot, sg);
     } else if (role == 1) {
         // ---- OSC (SynthVoice.h:44-45): Port::Process, Oscillator::SetFreq / Process, WAVE_POLYBLEP_SAW,
         //      amp 0.5 ----
@@ -192,8 +252,10 @@ __global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
         const float inv_sr = c[VCC_INV_SR * n + i];
         float freq = s[VCS_FREQ * n + i];
         float phase = s[VCS_PHASE * n + i], port_z = s[VCS_PORT_Z * n + i];
+        [[maybe_unused]] bool fset = false;               // SEG: some segment set the frequency
+        SegCursor<SEG> cu(sg, a.n_seg);
         for (uint32_t k = 0; k < nsteps; ++k) {
-            if (k == 1) {
+            if (!SEG && k == 1) {
                 // the block's pitch events (NoteOn: mtof(note), SetFrequency: Hz), staged by ENV
                 // before the first barrier; OSC's first chunk is step 1
                 const VoiceEv ev = staged_event(a, evslot, me);
@@ -203,8 +265,18 @@ __global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
                 }
             }
             if (k >= 1 && k + 1 < nsteps) {
+                if constexpr (SEG) {
+                    if (cu.first) {              // the segment's pitch events, staged by ENV before the first barrier
+                        const VoiceEv ev = seg_event(*sg, cu.seg, me);
+                        if (ev.op & VEV_FREQ) {
+                            freq = ev.freq;
+                            fset = true;
+                        }
+                    }
+                }
+                const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k - 1); }();
                 float *qo = &sq[(k - 1) & 1][0][lane];
-                if (len(k - 1) == (uint32_t)kVcChunk) {
+                if (m == (uint32_t)kVcChunk) {
                     // only Port and the phase are recurrences: run them for the chunk, then the
                     // polyBLEP saw per sample over four packed sample pairs (stage by stage, as FREQ)
                     constexpr int P = kVcChunk / 2;
@@ -259,7 +331,7 @@ __global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
                         qo[(2 * q + 1) * 64] = y.y;
                     }
                 } else {
-                    for (uint32_t j = 0; j < len(k - 1); ++j) {
+                    for (uint32_t j = 0; j < m; ++j) {
                         port_z = freq + port_c * (port_z - freq);
                         const float inc = port_z * inv_sr;
                         const float t = phase;
@@ -268,23 +340,34 @@ __global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) {
                         qo[j * 64] = saw_out(t, polyblep(inc, t));
                     }
                 }
+                cu.next();
             }
             __syncthreads();
         }
+        if constexpr (SEG)
+            if (fset) s[VCS_FREQ * n + i] = freq;         // the last segment's
         s[VCS_PHASE * n + i] = phase;
         s[VCS_PORT_Z * n + i] = port_z;
     } else if (role == 2) {
-        voice_role_freq(a, v, eq, fdq);
+        voice_role_freq<SEG>(a, v, eq, fdq, sg);
     } else {
         // chunk c's source samples: sq[c & 1], 64 floats apart
-        voice_role_filt<64>(a, v, eq, fdq, [&](uint32_t c2) { return &sq[c2 & 1][0][lane]; });
+        voice_role_filt<64, SEG>(a, v, eq, fdq, [&](uint32_t c2) { return &sq[c2 & 1][0][lane]; }, sg);
     }
 }
+__global__ __launch_bounds__(256) void voice_block_v5(VoiceArgs a) { voice_v5<false>(a); }
+__global__ __launch_bounds__(256) void voice_block_v5_seg(VoiceArgs a) { voice_v5<true>(a); }
 
 hipError_t launch_voice(const VoiceArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
     if ((uint64_t)kVcChunk * a.n * 4u > 0xFFFFFFFFull) return hipErrorInvalidValue;   // v5's chunk output resource
     const dim3 grid((a.n + 63) / 64);     // 64 voices per workgroup, one wave per role
+    if (a.n_seg > 1) {                    // timed events: the segmented kernels
+        if (a.n_seg > kSegCap || !a.seg || !a.ev) return hipErrorInvalidValue;
+        if (a.moog) hipLaunchKernelGGL(voice_block_v4_seg, grid, dim3(128), 0, s, a);
+        else hipLaunchKernelGGL(voice_block_v5_seg, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
     if (a.moog) hipLaunchKernelGGL(voice_block_v4, grid, dim3(128), 0, s, a);
     else hipLaunchKernelGGL(voice_block_v5, grid, dim3(256), 0, s, a);
     return hipGetLastError();

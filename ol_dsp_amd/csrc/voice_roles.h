@@ -87,6 +87,98 @@ __device__ __forceinline__ VoiceEv staged_event(const VoiceArgs &a, const uint2 
     return r;
 }
 
+// ---- timed events: a launch of several segments (olfx_layout.h kSegCap, VoiceArgs::seg) ----
+// A segmented kernel's block is the concatenation of its segments' chunks: chunking restarts at each
+// segment start, so every frame takes the arithmetic path it takes when each segment is a launch of its
+// own, and at a segment's first chunk a role does from registers what it does at a launch's start.
+// The LDS of such a kernel: the segments' bounds (start[n_seg] = n_frames) and every segment's staged
+// records, slot = voice within the group.  A slot set per segment, all staged before the first barrier:
+// a role that runs a step or two behind ENV reads a segment's records however short the segments are,
+// and the host-link reads of all segments are in flight together, ahead of the chunk loop.
+struct VoiceSegs {
+    uint32_t start[kSegCap + 1];
+    uint2 slot[kSegCap][64];
+};
+// The bounds, by the workgroup's first threads (the caller's next barrier publishes them); clamped to the
+// block, whatever the table holds.
+__device__ __forceinline__ void voice_segs_bounds(const VoiceArgs &a, VoiceSegs &sg) {
+    const uint32_t t = threadIdx.x, S = a.n_seg;
+    if (t <= S && t <= kSegCap) {
+        const uint32_t f = (t == 0u || t == S) ? 0u : a.seg[t];
+        sg.start[t] = t == S ? a.n_frames : (f < a.n_frames ? f : a.n_frames);
+    }
+}
+// Every segment's records of `group` into sg.slot, by one wave: all the fixed-slot reads first (one
+// host-link round trip for the lot), then the crowded segments' overflow runs (a second), then the slots.
+__device__ __forceinline__ void voice_events_stage(const VoiceArgs &a, VoiceSegs &sg, uint32_t lane, uint32_t group) {
+    const uint32_t S = a.n_seg < kSegCap ? a.n_seg : kSegCap;
+    const size_t per_seg = (size_t)((a.n + 63u) / 64u) * kVevCap;
+    uint2 e[kSegCap];
+#pragma unroll
+    for (uint32_t s = 0; s < kSegCap; ++s) {
+        e[s] = make_uint2(0u, 0u);
+        if (s < S && lane < kVevCap) e[s] = a.ev[s * per_seg + group * kVevCap + lane];
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < kSegCap; ++s) {
+        if (s < S) {
+            const uint32_t head = __builtin_amdgcn_readfirstlane(e[s].x);
+            if ((head >> 8) & VEV_MORE) {
+                const uint32_t cnt = head >> 16, first = __builtin_amdgcn_readfirstlane(e[s].y);
+                e[s] = make_uint2(0u, 0u);
+                if (lane < cnt) e[s] = a.ev_more[first + lane];
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < kSegCap; ++s) {
+        if (s < S) {
+            sg.slot[s][lane] = make_uint2(0u, 0u);
+            if (e[s].x >> 8) sg.slot[s][e[s].x & 63u] = make_uint2(e[s].x >> 8, e[s].y);
+        }
+    }
+    // as voice_event_of: one wave writes and reads its slots in order; other waves read after a barrier
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ VoiceEv seg_event(const VoiceSegs &sg, uint32_t seg, uint32_t me) {
+    const uint2 v = sg.slot[seg][me];
+    return VoiceEv{v.x, __uint_as_float(v.y)};
+}
+// A role's place in the launch's chunk sequence (wave-uniform): the chunk's first frame, its segment and
+// whether it starts it.  SEG = false: nothing (the roles index chunks by step, as they always have).
+template <bool SEG>
+struct SegCursor {
+    __device__ __forceinline__ SegCursor(const VoiceSegs *, uint32_t) {}
+    __device__ __forceinline__ uint32_t len() const { return 0u; }
+    __device__ __forceinline__ void next() {}
+    static constexpr uint32_t f0 = 0u, seg = 0u, end = 0u;
+    static constexpr bool first = false;
+};
+template <>
+struct SegCursor<true> {
+    const VoiceSegs *sg;
+    uint32_t n_seg, seg, f0, end;
+    bool first;
+    __device__ __forceinline__ SegCursor(const VoiceSegs *s, uint32_t n)
+        : sg(s), n_seg(n), seg(0u), f0(0u), end(__builtin_amdgcn_readfirstlane(s->start[1])), first(true) {}
+    __device__ __forceinline__ uint32_t len() const {
+        const uint32_t d = end - f0;
+        return d < (uint32_t)8 ? d : (uint32_t)8;          // kVcChunk (below)
+    }
+    __device__ __forceinline__ void next() {
+        f0 += len();
+        first = false;
+        if (f0 == end && seg + 1u < n_seg) {
+            ++seg;
+            const uint32_t e1 = __builtin_amdgcn_readfirstlane(sg->start[seg + 1u]);
+            end = e1 > f0 ? e1 : f0;                       // (ascending by the host's construction)
+            first = true;
+        }
+    }
+};
+
 // NoteOn / GateOn / NoteOff / GateOff on the envelope flags word and levels (SynthVoice.h:231-251):
 // Retrigger(true) = mode ATTACK and x = 0 for the amp (bits 0-2) and filter (bits 3-5) envelopes;
 // the gate is bit 8
@@ -102,7 +194,8 @@ __device__ __forceinline__ void apply_gate_events(const VoiceEv &ev, uint32_t &f
 }  // namespace
 
 // daisysp::Adsr as a segment machine.  The gate is constant inside a block (note events apply
-// between blocks), so the gate-edge test of Adsr::Process only fires on the block's first sample:
+// between blocks; with timed events, inside each of the block's event segments, and begin() runs at
+// every segment start), so the gate-edge test of Adsr::Process only fires on the first sample:
 // it is applied once in begin(), and each sample is the segment update x += d0 (target - x)
 // followed by the segment's clamp -- ATTACK ends above 1 (-> DECAY at x = 1), DECAY / RELEASE end
 // below 0 (-> IDLE at x = 0) -- which is v_med3(xn, lo, hi) with the segment's (lo, hi).  The
@@ -194,6 +287,7 @@ __device__ __forceinline__ void voice_envs_store(const VoiceEnvs &v, float *s, u
 // 2 of them) measured 2 % faster than 16 (18 steps) for the Svf voice and equal for the Moog
 // voice; 32 halves the workgroups per CU (96 KB of LDS each) and is 1.7x slower
 constexpr int kVcChunk = 8;
+static_assert(kVcChunk == 8 && kVoiceChunk == 8, "SegCursor<true>::len; the host's chunk count");
 
 // Runs f(j) for the m samples of a chunk: unrolled when the chunk is full, so the off-recurrence
 // work of neighbouring samples interleaves (ILP for a wave that is alone on its SIMD).
@@ -236,9 +330,20 @@ __device__ __forceinline__ VoiceLane voice_lane(const VoiceArgs &a) {
     v.nsteps = (v.nf + kVcChunk - 1) / kVcChunk + 2;
     return v;
 }
+// ... of a segmented launch: its chunks are the segments' (VoiceArgs::n_chunks)
+__device__ __forceinline__ VoiceLane voice_lane_seg(const VoiceArgs &a) {
+    VoiceLane v = voice_lane(a);
+    v.nsteps = a.n_chunks + 2;
+    return v;
+}
 
 // ---- ENV (SynthVoice.h:42,46-47): the amp and filter Adsr, the cutoff sum ----
-__device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLane &v, VoiceEnvQ &eq, uint2 *evslot) {
+// SEG (timed events): `evslot` is unused; the wave stages every segment's records into *sg, and at each
+// segment's first chunk applies that segment's gate events to the live flag bits and levels and runs
+// Env::begin again with the carried gprev -- what the next launch does from the stored state.
+template <bool SEG = false>
+__device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLane &v, VoiceEnvQ &eq, uint2 *evslot,
+                                               VoiceSegs *sg = nullptr) {
     const uint32_t n = v.n, lane = v.lane, i = v.i, me = v.me, nsteps = v.nsteps;
     const float *c = a.coef;
     float *s = a.state;
@@ -246,22 +351,52 @@ __device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLa
     // issued before the event read, so their latency hides under its host-link round trip
     uint32_t flags0 = __float_as_uint(s[VCS_FLAGS * n + i]);
     float xa0 = s[VCS_ENVA_X * n + i], xf0 = s[VCS_ENVF_X * n + i];
-    const VoiceEv ev = voice_event(a, evslot, lane, me);
-    apply_gate_events(ev, flags0, xa0, xf0);
-    const bool gate = (flags0 >> 8) & 1u;
+    if constexpr (SEG) {
+        voice_events_stage(a, *sg, lane, blockIdx.x);
+    } else {
+        const VoiceEv ev = voice_event(a, evslot, lane, me);
+        apply_gate_events(ev, flags0, xa0, xf0);
+    }
+    bool gate = (flags0 >> 8) & 1u;
     bool gprev_a = (flags0 >> 6) & 1u, gprev_f = (flags0 >> 7) & 1u;
     const float amp_amt = c[VCC_AMP_AMT * n + i], fc_max = c[VCC_FC_MAX * n + i];
     const float amp_half = 0.5f * amp_amt;       // FILT's Low() halving folded in (exact scaling)
     const float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
     Env ea, ef;
-    ea.begin(gate, gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * n + i],
-             c[VCC_ATK_TGT_A * n + i], c[VCC_DEC_D0A * n + i], c[VCC_REL_D0A * n + i], c[VCC_SUS_A * n + i]);
-    ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * n + i],
-             c[VCC_ATK_TGT_F * n + i], c[VCC_DEC_D0F * n + i], c[VCC_REL_D0F * n + i], c[VCC_SUS_F * n + i]);
+    // (SEG: the envelope coefficients stay in registers for the segment starts)
+    [[maybe_unused]] float ca[5], cf[5];
+    if constexpr (SEG) {
+        ca[0] = c[VCC_ATK_D0A * n + i]; ca[1] = c[VCC_ATK_TGT_A * n + i]; ca[2] = c[VCC_DEC_D0A * n + i];
+        ca[3] = c[VCC_REL_D0A * n + i]; ca[4] = c[VCC_SUS_A * n + i];
+        cf[0] = c[VCC_ATK_D0F * n + i]; cf[1] = c[VCC_ATK_TGT_F * n + i]; cf[2] = c[VCC_DEC_D0F * n + i];
+        cf[3] = c[VCC_REL_D0F * n + i]; cf[4] = c[VCC_SUS_F * n + i];
+    } else {
+        ea.begin(gate, gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * n + i],
+                 c[VCC_ATK_TGT_A * n + i], c[VCC_DEC_D0A * n + i], c[VCC_REL_D0A * n + i], c[VCC_SUS_A * n + i]);
+        ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * n + i],
+                 c[VCC_ATK_TGT_F * n + i], c[VCC_DEC_D0F * n + i], c[VCC_REL_D0F * n + i], c[VCC_SUS_F * n + i]);
+    }
+    SegCursor<SEG> cu(sg, a.n_seg);
     for (uint32_t k = 0; k < nsteps; ++k) {
         if (k + 2 < nsteps) {
+            if constexpr (SEG) {
+                if (cu.first) {
+                    if (k) {                     // the live state as the flags word and levels a launch would load
+                        flags0 = ea.mode | ef.mode << 3 | (uint32_t)gprev_a << 6 | (uint32_t)gprev_f << 7 | (uint32_t)gate << 8;
+                        xa0 = ea.x;
+                        xf0 = ef.x;
+                    }
+                    apply_gate_events(seg_event(*sg, cu.seg, me), flags0, xa0, xf0);
+                    gate = (flags0 >> 8) & 1u;
+                    gprev_a = (flags0 >> 6) & 1u;
+                    gprev_f = (flags0 >> 7) & 1u;
+                    ea.begin(gate, gprev_a, flags0 & 7u, xa0, ca[0], ca[1], ca[2], ca[3], ca[4]);
+                    ef.begin(gate, gprev_f, (flags0 >> 3) & 7u, xf0, cf[0], cf[1], cf[2], cf[3], cf[4]);
+                }
+            }
+            const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k); }();
             float2 *qo = &eq[k % 3][0][lane];
-            if (v.len(k) == (uint32_t)kVcChunk) {
+            if (m == (uint32_t)kVcChunk) {
                 // Full chunk: the envelopes run speculatively with no per-sample segment test
                 // (a branch on a lane vote per sample serialised the chunk); if any lane's
                 // segment ended inside the chunk -- a few chunks per note -- the chunk is
@@ -294,12 +429,13 @@ __device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLa
                     }
                 }
             } else {
-                for_chunk(v.len(k), [&](uint32_t j) {
+                for_chunk(m, [&](uint32_t j) {
                     const float amp = ea.step() * amp_half;
                     const float fe = ef.step();
                     qo[j * 64] = make_float2(amp, svf_fc(__builtin_fmaf(fe * 20000.0f, fenv_amt, cutoff), fc_max));
                 });
             }
+            cu.next();
         }
         __syncthreads();
     }
@@ -310,17 +446,21 @@ __device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLa
 }
 
 // ---- FREQ: Svf::SetFreq (its divisions use the hardware reciprocal, as in v4) ----
-__device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceLane &v, const VoiceEnvQ &eq, VoiceFreqQ &fdq) {
+template <bool SEG = false>
+__device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceLane &v, const VoiceEnvQ &eq, VoiceFreqQ &fdq,
+                                                const VoiceSegs *sg = nullptr) {
     const uint32_t n = v.n, lane = v.lane, i = v.i, nsteps = v.nsteps;
     const float *c = a.coef;
     const float damp_res = c[VCC_DAMP_RES * n + i];
     const float inv_2sr = 1.0f / (c[VCC_SR * n + i] * 2.0f);
+    SegCursor<SEG> cu(sg, a.n_seg);
     for (uint32_t k = 0; k < nsteps; ++k) {
         if (k >= 1 && k + 1 < nsteps) {
+            const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k - 1); }();
             const float2 *qi = &eq[(k - 1) % 3][0][lane];
             float2 *qo = &fdq[(k - 1) & 1][0][lane];
             // hands FILT (-damp, fq): its notch src - damp band is src + (-damp) band, exactly
-            if (v.len(k - 1) == (uint32_t)kVcChunk) {
+            if (m == (uint32_t)kVcChunk) {
                 // no recurrence here: two samples per packed operation, the chunk's four pairs
                 // stage by stage (a packed result read by the next instruction costs a wait
                 // state; four independent pairs fill them)
@@ -356,7 +496,7 @@ __device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceL
                     qo[(2 * q + 1) * 64] = make_float2(neg_damp(damp_res, lim.y), fq[q].y);
                 }
             } else {
-                for (uint32_t j = 0; j < v.len(k - 1); ++j) {
+                for (uint32_t j = 0; j < m; ++j) {
                     const float fc = qi[j * 64].y;
                     const float fcn = fc * inv_2sr;
                     const float arg = __builtin_fminf(fcn, 0.25f);
@@ -365,6 +505,7 @@ __device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceL
                     qo[j * 64] = make_float2(neg_damp(damp_res, lim), fq);
                 }
             }
+            cu.next();
         }
         __syncthreads();
     }
@@ -372,17 +513,19 @@ __device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceL
 
 // ---- FILT: Svf::Process; Low() = the average of the two passes' low outputs; * amp ----
 // src_of(c) = this lane's first source sample of chunk c; the chunk's samples are STRIDE floats apart.
-template <uint32_t STRIDE, class SrcOf>
+template <uint32_t STRIDE, bool SEG = false, class SrcOf>
 __device__ __forceinline__ void voice_role_filt(const VoiceArgs &a, const VoiceLane &v, const VoiceEnvQ &eq,
-                                                const VoiceFreqQ &fdq, SrcOf &&src_of) {
+                                                const VoiceFreqQ &fdq, SrcOf &&src_of, const VoiceSegs *sg = nullptr) {
     const uint32_t n = v.n, lane = v.lane, i = v.i, nsteps = v.nsteps;
     const float *c = a.coef;
     float *s = a.state;
     const float drive = c[VCC_DRIVE * n + i];
     float low = s[VCS_LOW * n + i], band = s[VCS_BAND * n + i];
+    SegCursor<SEG> cu(sg, a.n_seg);
     for (uint32_t k = 0; k < nsteps; ++k) {
         if (k >= 2) {
-            const uint32_t f0 = (k - 2) * kVcChunk;
+            const uint32_t f0 = SEG ? (uint32_t)cu.f0 : (k - 2) * kVcChunk;
+            const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k - 2); }();
             // the chunk's output rows through a buffer resource based at row f0: the row offset
             // j n 4 is a scalar (soffset), so a store costs no vector address arithmetic
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
@@ -390,7 +533,7 @@ __device__ __forceinline__ void voice_role_filt(const VoiceArgs &a, const VoiceL
             const float *qs = src_of(k - 2);
             const float2 *qa = &eq[(k - 2) % 3][0][lane];
             const float2 *qf = &fdq[k & 1][0][lane];           // chunk k-2: (k-2) & 1 == k & 1
-            for_chunk(v.len(k - 2), [&](uint32_t j) {
+            for_chunk(m, [&](uint32_t j) {
                 const float2 fd = qf[j * 64];
                 const float2 sa = make_float2(qs[j * STRIDE], qa[j * 64].x);
                 // (packing this serial recurrence's paired products cost as many register
@@ -409,6 +552,7 @@ __device__ __forceinline__ void voice_role_filt(const VoiceArgs &a, const VoiceL
                 // Low() = 0.5 low1 + 0.5 low2, times amp: (low1 + low2) (amp / 2), the same rounding (halvings exact)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((low1 + low) * sa.y), ro, i * 4u, j * n * 4u, 0);
             });
+            cu.next();
         }
         __syncthreads();
     }
