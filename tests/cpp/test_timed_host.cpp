@@ -2,8 +2,9 @@
  * tests/cpp/test_timed_host.cpp -- olfx_timed_events in the engine's HIP-free host core
  * (ol_dsp_amd/csrc/olfx_host.h) on the CPU: the pending list's order and its segments, each segment's fold
  * against the fold of a split queue, the carry-over arithmetic, validation (a refused call changes
- * nothing), the refusals per kind, a frame-0-only queue's packet against today's, and the worst packet
- * against max_packet_words.  Links olfx_host.cpp directly (no libolfx.so, no GPU); built by
+ * nothing), the refusals per kind, a frame-0-only queue's packet against today's, the worst packet
+ * against max_packet_words and its offsets at n = 1, 64, 65 and 8230, the span at exactly 16, 17, 32 and 33
+ * times, an event at frame == span, and the chunk count of ragged spans.  Links olfx_host.cpp directly (no libolfx.so, no GPU); built by
  * tests/test_timed_host.py with its own build line.
  */
 #include "../../ol_dsp_amd/csrc/olfx_host.h"
@@ -329,6 +330,153 @@ TEST(Timed, WorstPacketFitsTheMaximum) {
         EXPECT_EQ(host::max_segments(OLFX_KIND_SYNTH), 1u);
         EXPECT_EQ(host::max_segments(OLFX_KIND_DRUMKIT), 1u);
         EXPECT_EQ(host::max_segments(OLFX_KIND_FXRACK), 1u);
+    }
+}
+
+TEST(Timed, WorstPacketOffsetsBySize) {
+    /* every voice in each of kSegCap segments, every coefficient dirty, at n = 1 (one lane), 64 (one full group), 65
+       (a group of one voice, which fits its fixed slots) and 8230 (128 full groups and 38 voices: a segment's
+       records alone are past 64 KiB).  The section's offsets, restated: slots [kSegCap][groups][kVevCap], the
+       overflow list, the start frames -- and the maximum is reached exactly where every group is crowded */
+    const auto up4 = [](size_t w) { return (w + 3) & ~(size_t)3; };
+    for (const int kind : {OLFX_KIND_VOICE, OLFX_KIND_VOICE_MOOG, OLFX_KIND_VOICE_SAMPLE})
+        for (const uint32_t n : {1u, 64u, 65u, 8230u}) {
+            Shadow s;
+            s.init(kind, n, 48000.f);
+            s.reset();                                                     /* all dirty */
+            std::vector<olfx_timed_event> evs;
+            for (uint32_t k = 0; k < kSegCap; ++k)
+                for (uint32_t i = 0; i < n; ++i) evs.push_back(tev(4 * k, i, k & 1 ? OFF : ON, (uint8_t)(30 + (i + k) % 90)));
+            EXPECT_EQ(queue(s, evs), OLFX_OK);
+            EXPECT_EQ(s.span(64), 64u);
+            host::PacketPlan pl;
+            const std::vector<uint32_t> sec = section(s, 64, &pl);
+            const size_t groups = (n + 63) / 64, W = s.kd->words, fixw = 2 * groups * kVevCap;
+            const size_t tail = n % 64, crowded = (n / 64) * 64 + (tail > kVevCap ? tail : 0);
+            EXPECT_TRUE(pl.dense);
+            EXPECT_EQ(pl.n_seg, (size_t)kSegCap);
+            EXPECT_EQ(pl.o_val, (size_t)0);
+            EXPECT_EQ(pl.o_ev, up4(W * n));
+            EXPECT_EQ((size_t)s.n_more, kSegCap * crowded);
+            EXPECT_EQ(pl.o_seg, pl.o_ev + kSegCap * fixw + 2 * (size_t)s.n_more);
+            EXPECT_EQ(pl.words, pl.o_seg + kSegCap);
+            EXPECT_EQ(sec.size(), pl.words - pl.o_ev);
+            const size_t most = host::max_packet_words(kind, n, 0, kSegCap);
+            EXPECT_TRUE(pl.words <= most);
+            /* the maximum's event part: 2 * segs * (groups * kVevCap + n) + segs words */
+            const size_t ev_most = 2 * (size_t)kSegCap * (groups * kVevCap + n) + kSegCap;
+            if (crowded == n) {
+                EXPECT_EQ(sec.size(), ev_most);
+                EXPECT_TRUE(most - pl.words <= n + 16);                    /* the absent instance list, the slack */
+            } else {
+                EXPECT_EQ(sec.size() + 2 * (size_t)kSegCap * (n - crowded), ev_most);
+            }
+            if (n == 8230) EXPECT_TRUE(8 * (size_t)n >= 65536);
+            /* what was written there: the start frames, and every segment's records in voice order */
+            const uint32_t *more = sec.data() + kSegCap * fixw;
+            for (uint32_t k = 0; k < kSegCap; ++k) {
+                EXPECT_EQ(more[2 * s.n_more + k], 4 * k);
+                const std::vector<Rec> got = decode(sec.data() + k * fixw, more, n);
+                EXPECT_EQ(got.size(), (size_t)n);
+                bool ok = got.size() == n;
+                for (uint32_t i = 0; ok && i < n; ++i) {
+                    const bool gate = !(k & 1);
+                    ok = got[i].inst == i && (got[i].op & VEV_GATE_SET) && !(got[i].op & VEV_GATE_ON) == !gate &&
+                         !(got[i].op & VEV_RETRIGGER) == !gate;
+                }
+                EXPECT_TRUE(ok);
+            }
+            EXPECT_TRUE(s.timed.empty() && s.events.empty());
+        }
+}
+
+TEST(Timed, SpanAtTheCapExactly) {
+    /* 16, 17, 32 and 33 distinct times, frame 0 among them: one launch, 16 + 1, 16 + 16, 16 + 16 + 1 */
+    const uint32_t counts[] = {16, 17, 32, 33};
+    for (const uint32_t times : counts) {
+        Shadow s = fresh(OLFX_KIND_VOICE_SAMPLE, 70);
+        std::vector<olfx_timed_event> evs;
+        for (uint32_t k = 0; k < times; ++k) evs.push_back(tev(4 * k, k % 70, ON));
+        EXPECT_EQ(queue(s, evs), OLFX_OK);
+        const uint32_t total = 256;
+        std::vector<uint32_t> spans, segs;
+        for (uint32_t f0 = 0; f0 < total;) {
+            const uint32_t span = s.span(total - f0);
+            s.fold_segments(span);
+            spans.push_back(span);
+            segs.push_back(s.n_seg());
+            s.advance(span);
+            f0 += span;
+        }
+        const std::vector<uint32_t> want_spans = times == 16 ? std::vector<uint32_t>{256} : times == 17 ? std::vector<uint32_t>{64, 192}
+                                               : times == 32 ? std::vector<uint32_t>{64, 192} : std::vector<uint32_t>{64, 64, 128};
+        const std::vector<uint32_t> want_segs = times == 16 ? std::vector<uint32_t>{16} : times == 17 ? std::vector<uint32_t>{16, 1}
+                                              : times == 32 ? std::vector<uint32_t>{16, 16} : std::vector<uint32_t>{16, 16, 1};
+        EXPECT_TRUE(spans == want_spans);
+        EXPECT_TRUE(segs == want_segs);
+        EXPECT_TRUE(s.timed.empty() && s.events.empty());
+    }
+    /* the same 16 times past an empty frame 0 are 17 segments */
+    Shadow s = fresh(OLFX_KIND_VOICE, 70);
+    std::vector<olfx_timed_event> evs;
+    for (uint32_t k = 1; k <= 16; ++k) evs.push_back(tev(4 * k, k, ON));
+    EXPECT_EQ(queue(s, evs), OLFX_OK);
+    EXPECT_EQ(s.span(68), 64u);
+    EXPECT_EQ(s.span(64), 64u);
+}
+
+TEST(Timed, AdvanceWithAnEventAtTheSpan) {
+    /* frame == span is frame 0 of the next launch, whether the span is the call's length or the cap's cut */
+    Shadow s = fresh(OLFX_KIND_VOICE, 8);
+    EXPECT_EQ(queue(s, {tev(64, 1, ON, 61), tev(64, 2, OFF), tev(68, 3, ON), tev(60, 4, ON)}), OLFX_OK);
+    EXPECT_EQ(s.span(64), 64u);
+    s.fold_segments(64);
+    EXPECT_EQ(s.n_seg(), 2u);
+    s.advance(64);
+    EXPECT_EQ(s.events.size(), (size_t)2);
+    EXPECT_EQ(s.events[0].inst, 1u);
+    EXPECT_EQ(s.events[1].inst, 2u);
+    EXPECT_EQ(s.timed.size(), (size_t)1);
+    EXPECT_EQ(s.timed[0].frame, 4u);
+    EXPECT_TRUE(s.has_events(4));
+    s.reset();
+    std::vector<olfx_timed_event> evs;
+    for (uint32_t k = 0; k <= 16; ++k) evs.push_back(tev(4 * k, k % 8, ON, (uint8_t)(40 + k)));
+    EXPECT_EQ(queue(s, evs), OLFX_OK);
+    const uint32_t span = s.span(128);
+    EXPECT_EQ(span, 64u);
+    s.fold_segments(span);
+    EXPECT_EQ(s.n_seg(), kSegCap);
+    EXPECT_EQ(s.timed.size(), (size_t)1);
+    s.advance(span);
+    EXPECT_TRUE(s.timed.empty());
+    EXPECT_EQ(s.events.size(), (size_t)1);
+    EXPECT_EQ(s.events[0].note, 56);
+    EXPECT_EQ(s.span(64), 64u);
+    s.fold_segments(64);
+    EXPECT_EQ(s.n_seg(), 1u);
+    EXPECT_EQ(s.folded.size(), (size_t)1);
+}
+
+TEST(Timed, ChunksOfRaggedSpans) {
+    /* n_chunks is the sum over the segments of their frames in chunks of 8, the last one up to the span */
+    const uint32_t frames[] = {4, 16, 44, 48, 96};
+    for (const uint32_t span : {100u, 104u, 128u, 300u}) {
+        Shadow s = fresh(OLFX_KIND_VOICE_MOOG, 70);
+        for (const uint32_t f : frames) {
+            const olfx_timed_event e = tev(f, f % 70, ON);
+            EXPECT_EQ(s.timed_events(&e, 1), OLFX_OK);
+        }
+        EXPECT_EQ(s.span(span), span);
+        s.fold_segments(span);
+        EXPECT_EQ(s.n_seg(), 6u);
+        uint32_t want = 0;
+        for (uint32_t k = 0; k < 6; ++k) {
+            const uint32_t a = k ? frames[k - 1] : 0u, b = k < 5 ? frames[k] : span;
+            want += (b - a + 7) / 8;
+        }
+        EXPECT_EQ(s.n_chunks(span, 8), want);
+        EXPECT_TRUE(want > (span + 7) / 8);                                /* more than an unsegmented launch's */
     }
 }
 

@@ -31,7 +31,8 @@ SAMPLE_LENGTHS = [20, 1000]
 
 def sample_recs(n):
     recs = [(i, 0) if i % 2 == 0 else (i, 1, 1, 100 + i, 160 + i) for i in range(n)]
-    recs[7] = (7, None)
+    if n > 7:
+        recs[7] = (7, None)
     return recs
 
 

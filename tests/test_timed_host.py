@@ -25,7 +25,7 @@ def test_timed_host_core(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "8 tests, 0 failures" in r.stdout
+    assert "12 tests, 0 failures" in r.stdout
 
 
 def test_timed_events_abi():
