@@ -383,6 +383,12 @@ typedef struct olfx_timed_event {
     uint32_t frame;         /* multiple of 4, below 2^31 */
     olfx_voice_event ev;
 } olfx_timed_event;
+/* A note at a frame inside the block for an instrument (olfx_timed_notes): instrument-addressed, routed through
+   Polyvoice / the VoiceMap when the engine reaches its frame. */
+typedef struct olfx_timed_note {
+    uint32_t frame;         /* multiple of 4, below 2^31 */
+    olfx_event ev;
+} olfx_timed_note;
 
 /* ---- control changes (MIDI CC / hardware controls; corelib/cc_map.h numbers) ----
    The reference's UpdateMidiControl(control, 0..127) / UpdateHardwareControl(control, float)
@@ -529,12 +535,34 @@ int olfx_voice_events(olfx_engine *e, const olfx_voice_event *ev, uint32_t n);
    olfx_control, olfx_update, olfx_sample_voices and olfx_sample_bank still land at the block boundary,
    before frame 0's events; olfx_reset drops pending timed events with the untimed ones.
    OLFX_E_ARG (nothing is queued): a frame that is no multiple of 4 or not below 2^31, or a record
-   olfx_voice_events refuses.  OLFX_E_KIND: the synth kinds and the drum kit -- their Playing() and their
-   Polyvoice / VoiceMap routing change at the call, so which voice a later-framed note reaches would depend
-   on calls not yet made; timed routing needs a decision of its own.  OLFX_E_STATE: effect and meter kinds. */
+   olfx_voice_events refuses.  OLFX_E_KIND: the synth kinds and the drum kit -- these events address a voice,
+   and an instrument's notes are routed: olfx_timed_notes, below.  OLFX_E_STATE: effect and meter kinds. */
 int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n);
+/* Notes at a frame inside the block for OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF and OLFX_KIND_DRUMKIT.  The
+   contract of olfx_timed_events carries over: one olfx_process(N) computes, bit for bit in output and stored
+   state, what one process call per distinct event frame below N computes with that frame's notes handed to
+   olfx_note_events just before it, and olfx_synth_playing reads the same after both.  So a note is routed when
+   the engine reaches its frame, not at this call:
+     - a note at frame 0 is routed here and joins the untimed queue, exactly as olfx_note_events does (ties keep
+       call order);
+     - a note at frame f > 0 stays pending, unrouted, and is routed inside the olfx_process whose frames contain
+       f, in order of (frame, queueing order), against Playing() as the earlier frames' notes left it: a NoteOn
+       at frame 8 finds free the voice a NoteOff at frame 4 released, and a NoteOn with no free voice at its
+       frame is dropped, as Polyvoice drops it.  A drum kit uses the VoiceMap in force at that olfx_process:
+       olfx_drumkit_map between queueing and processing reroutes pending notes;
+     - a note at or past N stays pending with its frame reduced by N; one whose frame becomes 0 is routed as that
+       olfx_process returns, ahead of anything queued afterwards;
+     - GATE_ON / GATE_OFF fan out to every voice at their frame.
+   olfx_synth_playing is Playing() as of the frames processed so far, plus the frame-0 notes queued since.
+   Parameter, control, map and sample changes still land at the block boundary, before frame 0's notes;
+   olfx_reset drops pending timed notes.  A launch takes 16 distinct times; a call with more runs as several.
+   OLFX_E_ARG (nothing is queued, Playing() untouched): null with n > 0, a frame that is no multiple of 4 or
+   not below 2^31, or a record olfx_note_events refuses on that kind (inst out of range, note > 127,
+   type > GATE_OFF; a drum kit: type > NOTE_ON).  OLFX_E_KIND: the three voice kinds (olfx_timed_events).
+   OLFX_E_STATE: effect and meter kinds. */
+int olfx_timed_notes(olfx_engine *e, const olfx_timed_note *ev, uint32_t n);
 /* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF / OLFX_KIND_DRUMKIT: Playing() of the `voices` voices of instrument (kit) inst,
-   as of the calls made so far. */
+   as of the calls made so far (with timed notes: as of the frames processed so far). */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);
 
 /* Update() of instances [first, first + count) with their current parameters (SynthVoice.h:66-98,

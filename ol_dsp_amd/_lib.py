@@ -106,6 +106,13 @@ class TimedEvent(ctypes.Structure):
     ]
 
 
+class TimedNote(ctypes.Structure):
+    _fields_ = [
+        ("frame", ctypes.c_uint32),
+        ("ev", Event),
+    ]
+
+
 EV_NOTE_OFF, EV_NOTE_ON, EV_GATE_ON, EV_GATE_OFF, EV_SET_FREQUENCY = 0, 1, 2, 3, 4
 
 
@@ -176,6 +183,7 @@ SIGNATURES = {
     "olfx_note_events": (ctypes.c_int, [_P, ctypes.POINTER(Event), _U32]),
     "olfx_voice_events": (ctypes.c_int, [_P, ctypes.POINTER(VoiceEvent), _U32]),
     "olfx_timed_events": (ctypes.c_int, [_P, ctypes.POINTER(TimedEvent), _U32]),
+    "olfx_timed_notes": (ctypes.c_int, [_P, ctypes.POINTER(TimedNote), _U32]),
     "olfx_update": (ctypes.c_int, [_P, _U32, _U32]),
     "olfx_control_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_F)]),

@@ -1,5 +1,6 @@
 // ol_dsp_amd/csrc/drumkit.hip -- the reference's drum machine (a VoiceMap of sample voices, summed, into the
-// effect rack) in one launch, gfx950, wave64: drumkit_block_v1, OLFX_KIND_DRUMKIT.
+// effect rack) in one launch, gfx950, wave64: drumkit_block_v1 = drumkit_block<false>, OLFX_KIND_DRUMKIT (and
+// drumkit_block_v1_seg = drumkit_block<true>, the launch of a block with timed notes inside it).
 //
 // Per frame and kit, every operation in fp32:
 //   v[p]  = voice slot p: SynthVoice(SampleSoundSource<1>(Sample), SvfFilter) -- sampler_block_v1's arithmetic,
@@ -67,7 +68,11 @@ struct DkVoice : VoiceEnvs {
 };
 }  // namespace
 
-__global__ __launch_bounds__(sy::kThreads) void drumkit_block_v1(DrumkitArgs a) {
+// SEG (drumkit_block_v1_seg; olfx_timed_notes): the launch's frames are a.n_seg segments with note events of their
+// own; the V waves split their chunks at the segment starts (sy::role_v) and fetch per piece, so a cooperative load
+// never spans a Seek -- its latency is exposed once per segment start.  D and F are the same code.
+template <bool SEG>
+__global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const sy::Wg b = sy::enter(a, lds);
     const uint32_t P = b.P;
@@ -195,7 +200,20 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block_v1(DrumkitArgs a) 
                     if (k < m) q[k * 64u] = svf_voice_tick_src(v.ea, v.ef, v.low, v.band, x[k], v.kc);
             }
         };
-        sy::role_v<DkVoice, float[sy::kChunk]>(b, load, run, store, fetch);
+        if constexpr (SEG) {
+            // a segment's events on the live voice, as load applies the block's: the gate and the envelopes, Seek(0),
+            // Play() / Pause(), and the stored pitch (the last segment's value wins)
+            auto start = [&](DkVoice &v, uint32_t p, const VoiceEv &ev) {
+                const uint32_t si = p * a.npad + i;
+                voice_envs_restart(v, ev, c, sn, si);
+                if (ev.op & VEV_SEEK) v.pos = 0u;
+                if (ev.op & VEV_GATE_SET) v.playing = (ev.op & VEV_GATE_ON) != 0u;
+                if (ev.op & VEV_FREQ) s[VCS_FREQ * sn + si] = ev.freq;
+            };
+            sy::role_v<DkVoice, float[sy::kChunk], true>(b, load, run, store, fetch, &a, start);
+        } else {
+            sy::role_v<DkVoice, float[sy::kChunk]>(b, load, run, store, fetch);
+        }
     } else if (sy::is_d(b)) {
         const uint32_t order = a.order[sy::d_instrument(b)];   // the map is the block's: delivered ahead of the launch
         // VoiceMap::Process: frame = 0; frame += voice at the lowest mapped note; ... (one add per voice)
@@ -219,7 +237,7 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block_v1(DrumkitArgs a) 
 hipError_t launch_drumkit(const DrumkitArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
     if (!instrument_args_ok(a, kDkMaxVoices) || (a.bank_bytes && !a.bank)) return hipErrorInvalidValue;
-    return sy::launch(drumkit_block_v1, a, kDkTile, s);
+    return sy::launch(a.n_seg > 1u ? drumkit_block<true> : drumkit_block<false>, a, kDkTile, s);
 }
 
 }  // namespace olfx

@@ -572,6 +572,8 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.npad = e->hs.npad;
         a.ev = ev.ev;
         a.ev_more = ev.ev_more;
+        a.n_seg = ev.n_seg;               // timed notes: the *_seg kernel
+        a.seg = ev.seg;
     };
     switch (e->kind) {
     case OLFX_KIND_DATTORRO: {
@@ -717,8 +719,12 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
 // are >= 4 GiB apart, tiles are staged through a compact device buffer.  Frames run in order and
 // the state carries between launches, so tiles compute exactly what one launch would.  The note
 // events apply before the first tile (the block's start).
-int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, hipStream_t s, const VoiceArgs &ev) {
-    const uint64_t n = e->n, plane = (uint64_t)n_frames * n;
+// `call_frames`: the frames of the whole olfx_process call, of which these n_frames are a run (timed events at
+// more times than a launch takes: in / out point at the run's first frame, and the channel planes keep the
+// call's distance).
+int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, uint32_t call_frames, hipStream_t s,
+               const VoiceArgs &ev) {
+    const uint64_t n = e->n, plane = (uint64_t)call_frames * n;
     const uint64_t lim = (1ull << 30) - 1;                     // floats addressable in 32-bit bytes
     const VoiceArgs none{};
     if (!e->hs.kd->planes_32bit || plane + plane <= lim) {
@@ -899,7 +905,8 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     // slots allocated now, so that no block -- an all-voices note-off in the middle of a stream,
     // say -- pays a pinned / device allocation: the small ones at the copy threshold, the big ones
     // for the largest packet this engine can produce (up to 256 MiB each; larger on first need)
-    const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev(), host::max_segments(kind));
+    const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev(),
+                                               std::max(host::max_segments(kind), host::max_note_segments(kind)));
     for (olfx_engine::Slot &sl : e->slot)
         if (!rc) rc = grow_slot(e, sl, olfx_engine::kCopyBytes / 4, false);
     if (maxw * 4 >= e->copy_bytes && maxw * 4 <= ((size_t)256 << 20))
@@ -995,6 +1002,10 @@ int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n) {
     return e ? e->report(e->hs.timed_events(ev, n)) : OLFX_E_ARG;
 }
 
+int olfx_timed_notes(olfx_engine *e, const olfx_timed_note *ev, uint32_t n) {
+    return e ? e->report(e->hs.timed_notes(ev, n)) : OLFX_E_ARG;
+}
+
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing) {
     return e ? e->report(e->hs.synth_playing(inst, playing)) : OLFX_E_ARG;
 }
@@ -1025,8 +1036,9 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
     }
     // the block's parameter changes and note events: asynchronous, O(changed)
     // One pass over all the frames -- unless timed events sit at more distinct frames than a launch takes
-    // segments (host::Shadow::span: the voice kinds, one output plane and no input): then a pass per run of
-    // segments, each with its own packet, the state carrying between them as between run_frames' tiles.
+    // segments (host::Shadow::span: the voice kinds and the instrument kinds, no input): then a pass per run of
+    // segments, each with its own packet, the state carrying between them as between run_frames' tiles.  A run
+    // writes its frames of every output plane: the planes stay the whole call's distance apart.
     const bool host_io = io_flags == OLFX_IO_HOST;
     const float *const rin = host_io ? (fin ? e->d_in : nullptr) : in;
     float *const rout = host_io ? (summary ? nullptr : e->d_out) : out;
@@ -1041,7 +1053,7 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
             const hipError_t r = hipMemcpyAsync(e->d_in, e->h_in, fin * 4, hipMemcpyHostToDevice, s);
             if (r != hipSuccess) rc = e->hip_fail(r, "olfx_process: input copy");
         }
-        if (!rc) rc = run_frames(e, rin, rout ? rout + (size_t)f0 * e->n : nullptr, span, s, ev);
+        if (!rc) rc = run_frames(e, rin, rout ? rout + (size_t)f0 * e->n : nullptr, span, n_frames, s, ev);
         launched_on(e, s);
         // the slot is free again once whatever was queued on `s` (the scatter, the kernels) is done --
         // recorded on the error paths too, so a later block never overwrites a packet still being read

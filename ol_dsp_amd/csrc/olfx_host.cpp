@@ -517,6 +517,7 @@ uint32_t in_channels(int kind) { return kind_desc(kind).in_ch; }
 uint32_t out_channels(int kind) { return kind_desc(kind).out_ch; }
 bool takes_note_events(int kind) { return kind_desc(kind).takes_note_events(); }
 uint32_t max_segments(int kind) { return kind_desc(kind).instances == KindDesc::VOICES ? kSegCap : 1u; }
+uint32_t max_note_segments(int kind) { return kind_desc(kind).instances == KindDesc::INSTRUMENTS ? kSegCap : 1u; }
 double algorithmic_bytes_per_frame(int kind) { return kind_desc(kind).bytes_per_frame; }
 double algorithmic_read_bytes_per_frame(int kind) { return kind_desc(kind).read_bytes_per_frame; }
 
@@ -1045,8 +1046,8 @@ int Shadow::note_events(const olfx_event *ev, uint32_t count) {
             return fail(OLFX_E_ARG, "olfx_note_events: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
     }
     for (uint32_t k = 0; k < count; ++k) {
-        if (kit()) route_kit(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
-        else if (instruments()) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        if (kit()) route_kit(events, ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        else if (instruments()) route_synth(events, ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         else events.push_back(olfx_voice_event{ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity, 0, 0.f});
     }
     return OLFX_OK;
@@ -1063,11 +1064,11 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
             return fail(OLFX_E_ARG, "olfx_voice_events: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
     }
     if (kit()) {
-        for (uint32_t k = 0; k < count; ++k) route_kit(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        for (uint32_t k = 0; k < count; ++k) route_kit(events, ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         return OLFX_OK;
     }
     if (instruments()) {
-        for (uint32_t k = 0; k < count; ++k) route_synth(ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
+        for (uint32_t k = 0; k < count; ++k) route_synth(events, ev[k].inst, ev[k].type, ev[k].note, ev[k].velocity);
         return OLFX_OK;
     }
     events.insert(events.end(), ev, ev + count);
@@ -1076,9 +1077,8 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
 
 int Shadow::timed_events(const olfx_timed_event *ev, uint32_t count) {
     if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_timed_events: not a voice engine");
-    // Playing() and the Polyvoice / VoiceMap routing change at the call: which voice a later-framed note
-    // reaches would depend on calls not yet made
-    if (instruments()) return fail(OLFX_E_KIND, "olfx_timed_events: the synth kinds and the drum kit route notes at the call");
+    // voice-addressed events; an instrument's notes are routed, at their frame: olfx_timed_notes
+    if (instruments()) return fail(OLFX_E_KIND, "olfx_timed_events: the synth kinds and the drum kit take olfx_timed_notes");
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_timed_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         const olfx_voice_event &v = ev[k].ev;
@@ -1095,9 +1095,37 @@ int Shadow::timed_events(const olfx_timed_event *ev, uint32_t count) {
         if (ev[k].frame == 0u) events.push_back(ev[k].ev);
         else timed.push_back(ev[k]);
     }
+    merge_timed(old);
+    return OLFX_OK;
+}
+
+void Shadow::merge_timed(size_t old) {
     const auto by_frame = [](const olfx_timed_event &x, const olfx_timed_event &y) { return x.frame < y.frame; };
     std::stable_sort(timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
     std::inplace_merge(timed.begin(), timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
+}
+
+// Timed notes of the synths and the drum kit.  A note is routed when the engine reaches its frame: a note at
+// frame 0 here, as olfx_note_events routes it; a later one stays pending, unrouted (fold_segments, advance).
+int Shadow::timed_notes(const olfx_timed_note *ev, uint32_t count) {
+    if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_timed_notes: not a synth or drum kit engine");
+    if (!instruments()) return fail(OLFX_E_KIND, "olfx_timed_notes: the voice kinds take olfx_timed_events");
+    if (count && !ev) return fail(OLFX_E_ARG, "olfx_timed_notes: null events");
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_event &v = ev[k].ev;
+        if ((ev[k].frame & 3u) || ev[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_notes: event %u: frame %u (a multiple of 4 below 2^31)", k, ev[k].frame);
+        if (v.inst >= n || v.note > 127 || v.type > OLFX_EV_GATE_OFF) return fail(OLFX_E_ARG, "olfx_timed_notes: bad event %u", k);
+        if (kit() && v.type > OLFX_EV_NOTE_ON)
+            return fail(OLFX_E_ARG, "olfx_timed_notes: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
+    }
+    const size_t old = timed.size();
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_voice_event v{ev[k].ev.inst, ev[k].ev.type, ev[k].ev.note, ev[k].ev.velocity, 0, 0.f};
+        if (ev[k].frame == 0u) route_note(events, v);
+        else timed.push_back(olfx_timed_event{ev[k].frame, v});
+    }
+    merge_timed(old);
     return OLFX_OK;
 }
 
@@ -1118,7 +1146,11 @@ void Shadow::advance(uint32_t span_) {
     size_t k = 0;
     for (olfx_timed_event &t : timed) {
         t.frame = t.frame > span_ ? t.frame - span_ : 0u;
-        if (!t.frame) events.push_back(t.ev), ++k;        // (ahead of anything queued from now on)
+        if (!t.frame) {                                   // (ahead of anything queued from now on)
+            if (instruments()) route_note(events, t.ev);
+            else events.push_back(t.ev);
+            ++k;
+        }
     }
     timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
 }
@@ -1135,9 +1167,9 @@ uint32_t Shadow::n_chunks(uint32_t span_, uint32_t chunk) const {
 // 245-260: NoteOn stores the note, NoteOff stores 0).  The reference's quirks follow from the same
 // tests: NoteOn(0) leaves Playing() at 0, so the voice is gated yet still "free"; NoteOff(0) matches
 // the first voice with Playing() == 0.
-void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
+void Shadow::route_synth(std::vector<olfx_voice_event> &to, uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
     auto push = [&](uint32_t p) {
-        events.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
+        to.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
     };
     uint8_t *pl = playing.data() + inst;                 // voice p: pl[p * n]
     switch (type) {
@@ -1167,10 +1199,10 @@ void Shadow::route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velo
 
 // ol::synth::VoiceMap's NoteOn / NoteOff on kit `inst` (VoiceMap.h:27-43): the voice at note2voice[note] gets the
 // call, a note nobody sits at is ignored.  Playing() as in route_synth.
-void Shadow::route_kit(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
+void Shadow::route_kit(std::vector<olfx_voice_event> &to, uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity) {
     const uint8_t p = note2voice[(size_t)note * n + inst];
     if (p == kNoVoice) return;
-    events.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
+    to.push_back(olfx_voice_event{p * npad + inst, type, note, velocity, 0, 0.f});
     playing[(size_t)p * n + inst] = type == OLFX_EV_NOTE_ON ? note : 0;
 }
 
@@ -1273,7 +1305,13 @@ void Shadow::fold_segments(uint32_t span_) {
         size_t k1 = k;
         while (k1 < timed.size() && timed[k1].frame == timed[k].frame) ++k1;
         seg_frame.push_back(timed[k].frame);
-        fold_one(&timed[k].ev, k1 - k, sizeof(olfx_timed_event));
+        if (instruments()) {                              // routed now, against Playing() as the frames before left it
+            routed.clear();
+            for (size_t j = k; j < k1; ++j) route_note(routed, timed[j].ev);
+            fold_one(routed.data(), routed.size(), sizeof(olfx_voice_event));
+        } else {
+            fold_one(&timed[k].ev, k1 - k, sizeof(olfx_timed_event));
+        }
         seg_first.push_back((uint32_t)folded.size());
         k = k1;
     }

@@ -116,6 +116,9 @@ PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_mo
 size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0, uint32_t n_seg = 1);
 // the segments one launch of a kind can take: kSegCap for the kinds olfx_timed_events accepts, else 1
 uint32_t max_segments(int kind);
+// ... for the kinds olfx_timed_notes accepts (the synths and the drum kit): kSegCap, else 1.  An engine's packet
+// slots are sized by the larger of the two
+uint32_t max_note_segments(int kind);
 
 struct Folded { uint32_t inst, op, freq, pad; };
 
@@ -184,7 +187,11 @@ struct Shadow {
     std::vector<olfx_voice_event> events; // queued for the next block (its frame 0)
     // olfx_timed_events: the events past frame 0, stably ordered by frame (frames count from the next block's
     // first frame; an event at frame 0 goes to `events`, which keeps the queueing order across both calls)
+    // olfx_timed_notes (the synths and the drum kit, which take no timed voice events): the same list holds the
+    // pending instrument notes, unrouted -- ev.inst is the instrument, and the note is routed through Polyvoice /
+    // the VoiceMap when the engine reaches its frame (fold_segments, advance)
     std::vector<olfx_timed_event> timed;
+    std::vector<olfx_voice_event> routed; // fold_segments: one segment's notes as voice events
     // fold_events / fold_segments: one record per voice and segment, segment by segment and by first
     // appearance; segment s is folded[seg_first[s] .. seg_first[s + 1]) and starts at frame seg_frame[s]
     std::vector<Folded> folded;
@@ -238,6 +245,7 @@ struct Shadow {
     int note_events(const olfx_event *ev, uint32_t count);
     int voice_events(const olfx_voice_event *ev, uint32_t count);
     int timed_events(const olfx_timed_event *ev, uint32_t count);
+    int timed_notes(const olfx_timed_note *ev, uint32_t count);
     // The frames of the next launch of a block of n_frames: all of them, unless more than kSegCap distinct
     // event times lie in it (frame 0 included, with or without events) -- then up to the first time that
     // does not fit.
@@ -245,7 +253,8 @@ struct Shadow {
     // whether a launch of `span` frames has events
     bool has_events(uint32_t span_) const { return !events.empty() || (!timed.empty() && timed.front().frame < span_); }
     // After a launch of `span` frames: the pending events' frames count from the next launch (an event at
-    // frame `span` is at its frame 0).  fold_segments(span) has taken the events below `span`.
+    // frame `span` is at its frame 0).  fold_segments(span) has taken the events below `span`.  An instrument
+    // note that reaches frame 0 is routed here, ahead of anything queued from now on.
     void advance(uint32_t span_);
     int synth_playing(uint32_t inst, uint8_t *out);                  // [voices]
     // olfx_drumkit_map: VoiceMap::SetVoice records in order, judged on the state after the last
@@ -269,7 +278,9 @@ struct Shadow {
     // The queued events as one record per voice (`folded`) and their place in the event section.
     void fold_events();
     // The same for a launch of `span` frames: segment 0 is the frame-0 queue (it may be empty), then one
-    // segment per distinct frame of the timed events below `span`, which leave the pending list.
+    // segment per distinct frame of the timed events below `span`, which leave the pending list.  Instrument
+    // notes are routed here, frame by frame in (frame, queueing order), against Playing() as the earlier frames
+    // left it and the VoiceMap in force now; a segment whose notes were all dropped is an empty segment.
     void fold_segments(uint32_t span_);
     uint32_t n_seg() const { return (uint32_t)seg_frame.size(); }
     // the launch's chunks (VoiceArgs::n_chunks): each segment's frames in chunks of `chunk`
@@ -297,9 +308,16 @@ private:
     // kind: exactly those voice slots), and what must be re-derived
     void touched(uint32_t inst, uint32_t field0, uint32_t n_fields);
     // the kit's VoiceMap router (VoiceMap.h:27-43): a note event -> the event of the voice at that note
-    void route_kit(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
+    void route_kit(std::vector<olfx_voice_event> &to, uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
     // the synth's Polyvoice router (Polyvoice.h:35-77): one instrument event -> per-voice events
-    void route_synth(uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
+    void route_synth(std::vector<olfx_voice_event> &to, uint32_t inst, uint8_t type, uint8_t note, uint8_t velocity);
+    // either, by the kind
+    void route_note(std::vector<olfx_voice_event> &to, const olfx_voice_event &ev) {
+        if (kit()) route_kit(to, ev.inst, ev.type, ev.note, ev.velocity);
+        else route_synth(to, ev.inst, ev.type, ev.note, ev.velocity);
+    }
+    // the pending list whose entries from `old` on are new: stably by frame, behind the queued ones of their frame
+    void merge_timed(size_t old);
     // one segment's events onto `folded`, ev_count and ev_more
     void fold_one(const olfx_voice_event *ev, size_t count, size_t stride);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())

@@ -318,11 +318,17 @@ struct InstrumentArgs {
     uint32_t voices, npad;
     const uint2 *ev;            // [voices * npad / 64][kVevCap] fixed slots (nullptr: no events)
     const uint2 *ev_more;
+    // timed notes (olfx_timed_notes; olfx_layout.h kSegCap): n_seg >= 2 segments, segment s starting at frame
+    // seg[s] (seg[0] = 0, ascending, multiples of 4 below n_frames) with the fixed slots
+    // ev[s (voices npad / 64) kVevCap ..] -- the *_seg kernels.  n_seg <= 1: one segment, the launch as it was
+    uint32_t n_seg;
+    const uint32_t *seg;
 };
 // what both launches require of a non-empty block
 inline bool instrument_args_ok(const InstrumentArgs &a, uint32_t max_voices) {
     return !(a.n_frames & 3u) && !(a.t0 & 1u) && a.t0 < kFrMaxDelay && a.voices >= 1u && a.voices <= max_voices &&
-           a.npad == ((a.n + 63u) & ~63u) && a.plane >= (uint64_t)a.n_frames * a.n;
+           a.npad == ((a.n + 63u) & ~63u) && a.plane >= (uint64_t)a.n_frames * a.n &&
+           (a.n_seg <= 1u || (a.n_seg <= kSegCap && a.seg && a.ev));          // a segmented launch's table is there
 }
 
 // The synth (synth.hip): `voices` MoogFilter SynthVoices per instrument, their Polyvoice sum, the

@@ -1,8 +1,9 @@
 // ol_dsp_amd/csrc/synth.hip -- a whole polyphonic instrument (voices, Polyvoice sum, effect rack) in
-// one launch, gfx950, wave64.  One kernel template over the voice type, synth_block<SVF>, whose two
-// instantiations go by the names olfx_kernel_name reports:
+// one launch, gfx950, wave64.  One kernel template over the voice type, synth_block<SVF, SEG>, whose
+// instantiations go by the names olfx_kernel_name reports (SEG: the same name with _seg, the launch of a block
+// with timed notes inside it):
 //
-// synth_block_v1 = synth_block<false> (OLFX_KIND_SYNTH): the Daisy synth firmware's audio callback
+// synth_block_v1 = synth_block<false, false> (OLFX_KIND_SYNTH): the Daisy synth firmware's audio callback
 // (ol_daisy/app/synth/main.cpp:78-86):
 //
 //   mono = 0; voice.Process(&mono);       Polyvoice over P x SynthVoice(OscillatorSoundSource, MoogFilter)
@@ -20,7 +21,7 @@
 // which is what voice_block_v4 + voice_mix + fxrack_block_v3 at OLFX_FR_TOPOLOGY 1 compute in three
 // launches, bit for bit; the voice samples and the sum stay in LDS.
 //
-// synth_svf_block_v1 = synth_block<true> (OLFX_KIND_SYNTH_SVF): the library's own voice, SynthVoice(OscillatorSoundSource,
+// synth_svf_block_v1 = synth_block<true, false> (OLFX_KIND_SYNTH_SVF): the library's own voice, SynthVoice(OscillatorSoundSource,
 // SvfFilter), behind the same Polyvoice, into the rack at the instrument's topology:
 //   v[p]  = voice p: voice_block_v5's arithmetic, operation for operation (svf_voice.h)
 //   topology 1: as above
@@ -66,7 +67,10 @@ struct SySvfVoice : VoiceEnvs {
 
 // SVF: SvfFilter voices and the rack's topology per instrument, 0 or 1 (synth_svf_block_v1); else
 // MoogFilter voices and topology 1 (synth_block_v1).
-template <bool SVF>
+// SEG (synth_block_v1_seg, synth_svf_block_v1_seg; olfx_timed_notes): the launch's frames are a.n_seg segments
+// with note events of their own; the V waves split their chunks at the segment starts (sy::role_v), D and F are
+// the same code.  The per-sample voice functions make the pieces bit-exact with a launch per segment.
+template <bool SVF, bool SEG>
 __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const sy::Wg b = sy::enter(a, lds);
@@ -145,7 +149,19 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
                 for (uint32_t k = 0; k < m; ++k) tick(k);
             }
         };
-        sy::role_v<V>(b, load, run, store);
+        if constexpr (SEG) {
+            // a segment's events on the live voice: the gate and the envelopes, and NoteOn's pitch
+            auto start = [&](V &v, uint32_t, const VoiceEv &ev) {
+                voice_envs_restart(v, ev, c, n, i);
+                if (ev.op & VEV_FREQ) {
+                    v.freq = ev.freq;
+                    v.set_freq = true;
+                }
+            };
+            sy::role_v<V, true>(b, load, run, store, &a, start);
+        } else {
+            sy::role_v<V>(b, load, run, store);
+        }
     } else if (sy::is_d(b)) {
         // Polyvoice::Process: mono = 0; mono += v[0]; ... mono += v[P-1]
         sy::role_d<SVF>(b, a, [&](const float *q, float (&m)[sy::kChunk]) {
@@ -162,7 +178,8 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
 hipError_t launch_synth(const SynthArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
     if (!instrument_args_ok(a, kSyMaxVoices)) return hipErrorInvalidValue;
-    return sy::launch(a.svf ? synth_block<true> : synth_block<false>, a, 0, s);
+    if (a.n_seg > 1u) return sy::launch(a.svf ? synth_block<true, true> : synth_block<false, true>, a, 0, s);
+    return sy::launch(a.svf ? synth_block<true, false> : synth_block<false, false>, a, 0, s);
 }
 
 }  // namespace olfx

@@ -35,6 +35,7 @@
 #pragma once
 #include "rack_delay_stage.h"
 #include "lds_flags.h"
+#include "voice_roles.h"
 
 namespace olfx {
 namespace sy {
@@ -108,8 +109,19 @@ __device__ __forceinline__ uint32_t d_instrument(const Wg &b) {
 // load(v, p) / store(v, p): voice slot p's state into and out of v; fetch(v, m, x): what the voice can do for a
 // chunk of m frames ahead of the queue-V wait, its latency hidden under the previous chunk's consumers, handed on
 // in an X; run(v, x, q, m): the voice's samples of that chunk -> q[k * 64] (its column of queue V).
-template <class V, class X, class Load, class Run, class Store, class Fetch>
-__device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store, Fetch &&fetch) {
+//
+// SEG (timed notes, the *_seg kernels; a = the launch's arguments): only this role sees note events -- D and F are
+// continuous in time -- so the chunk grid, the queues, every counter and every wait stay as they are, and a V wave
+// splits a chunk's frames at the segment starts that fall inside it (multiples of 4: they can fall in mid-chunk).
+// The pieces' samples go to the same queue-V columns, q[(k0 + k) * 64]; the wave waits once and publishes F_V
+// once per chunk, as without segments.  At a segment start, for va and vb in turn, start(v, p, ev) does from
+// registers what load does at a launch's start (voice_envs_restart and the voice's own events).  fetch runs per
+// piece -- the first piece's ahead of the wait, as ever -- so nothing fetched spans a segment start.  The next
+// segment's records and start frame are read one segment ahead (seg_event_fetch); the starts are clamped to the
+// block and forced to ascend, whatever the table holds, so a piece is 1 .. m frames inside its chunk.
+template <class V, class X, bool SEG = false, class Load, class Run, class Store, class Fetch, class Start = std::nullptr_t>
+__device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store, Fetch &&fetch,
+                                       const InstrumentArgs *a = nullptr, Start &&start = nullptr) {
     const uint32_t wib = b.wib;
     if (wib >= b.nvw) return;
     const bool two = wib + (uint32_t)kVWaves < b.P;
@@ -117,28 +129,76 @@ __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Stor
     load(va, wib);
     if (two) load(vb, wib + kVWaves);
     else vb = va;                                          // (never run, never stored)
+    // SEG: the next segment, its start frame and its records of this wave's one or two voice-slot groups
+    [[maybe_unused]] uint32_t sgi = 1u, S = 1u, nb = b.nf, gpa = 0u, gpb = 0u, groups = 0u, me = 0u;
+    [[maybe_unused]] uint2 pa = make_uint2(0u, 0u), pb = make_uint2(0u, 0u);
+    [[maybe_unused]] uint2 *slots = b.evslots + wib * 64u;
+    [[maybe_unused]] auto ahead = [&] {
+        if (sgi < S) {
+            const uint32_t f = a->seg[sgi], lo = nb;       // (nb: the previous start)
+            pa = seg_event_fetch(a->ev, sgi, groups, gpa, b.lane);
+            if (two) pb = seg_event_fetch(a->ev, sgi, groups, gpb, b.lane);
+            nb = min(max(f, lo), b.nf);
+        } else {
+            nb = b.nf;
+        }
+    };
+    if constexpr (SEG) {
+        S = min(a->n_seg, kSegCap);
+        groups = b.P * (a->npad >> 6);
+        gpa = wib * (a->npad >> 6) + b.g;
+        gpb = (wib + kVWaves) * (a->npad >> 6) + b.g;
+        me = v_instrument(b) - b.g * 64u;
+        nb = 0u;
+        ahead();
+    }
     for (uint32_t ck = 0; ck < b.nchunks; ++ck) {
         const uint32_t m = min((uint32_t)kChunk, b.nf - ck * kChunk);
-        X xa, xb;
-        fetch(va, m, xa);
-        if (two) fetch(vb, m, xb);
-        wait([&] {
-            return flag_get(b.flags + F_R0) + kDepthV > ck && (!b.d1_on || flag_get(b.flags + F_R1) + kDepthV > ck);
-        });
         float *q = b.vq + (size_t)(ck % kDepthV) * b.P * kQ + b.lane;
-        run(va, xa, q + wib * kQ, m);
-        if (two) run(vb, xb, q + (wib + kVWaves) * kQ, m);
+        auto taken = [&] {                                 // the chunk's queue-V buffer was taken by D0 and D1
+            return flag_get(b.flags + F_R0) + kDepthV > ck && (!b.d1_on || flag_get(b.flags + F_R1) + kDepthV > ck);
+        };
+        if constexpr (!SEG) {
+            X xa, xb;
+            fetch(va, m, xa);
+            if (two) fetch(vb, m, xb);
+            wait(taken);
+            run(va, xa, q + wib * kQ, m);
+            if (two) run(vb, xb, q + (wib + kVWaves) * kQ, m);
+        } else {
+            const uint32_t f0 = ck * kChunk;
+            bool waited = false;
+            for (uint32_t k0 = 0; k0 < m;) {
+                while (sgi < S && nb == f0 + k0) {         // a segment starts at this frame
+                    start(va, wib, seg_event_take(pa, a->ev_more, slots, b.lane, me));
+                    if (two) start(vb, wib + kVWaves, seg_event_take(pb, a->ev_more, slots, b.lane, me));
+                    ++sgi;
+                    ahead();
+                }
+                // (nb > f0 + k0 now, or no segment is left and nb = nf: the piece has a frame at least)
+                const uint32_t k1 = sgi < S ? min(m, nb - f0) : m, len = k1 - k0;
+                X xa, xb;
+                fetch(va, len, xa);
+                if (two) fetch(vb, len, xb);
+                if (!waited) wait(taken);
+                waited = true;
+                run(va, xa, q + wib * kQ + k0 * 64u, len);
+                if (two) run(vb, xb, q + (wib + kVWaves) * kQ + k0 * 64u, len);
+                k0 = k1;
+            }
+        }
         flag_put(b.flags + F_V0 + wib, ck + 1);
     }
     store(va, wib);
     if (two) store(vb, wib + kVWaves);
 }
 // a voice with nothing to fetch: run(v, q, m)
-template <class V, class Load, class Run, class Store>
-__device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store) {
+template <class V, bool SEG = false, class Load, class Run, class Store, class Start = std::nullptr_t>
+__device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store, const InstrumentArgs *a = nullptr,
+                                       Start &&start = nullptr) {
     struct None {};
-    role_v<V, None>(
-        b, load, [&](V &v, None &, float *q, uint32_t m) { run(v, q, m); }, store, [](V &, uint32_t, None &) {});
+    role_v<V, None, SEG>(
+        b, load, [&](V &v, None &, float *q, uint32_t m) { run(v, q, m); }, store, [](V &, uint32_t, None &) {}, a, start);
 }
 
 // ---------------- D: the delay stage, per (instrument, channel) lane ----------------

@@ -283,6 +283,48 @@ __device__ __forceinline__ void voice_envs_store(const VoiceEnvs &v, float *s, u
                                              (uint32_t)v.gprev_f << 7 | (uint32_t)v.gate << 8);
 }
 
+// ---- timed notes in the instrument kernels (synth_pipeline.h role_v<SEG>; olfx_timed_notes) ----
+// The voice kernels stage every segment's records in LDS up front (VoiceSegs, 8 KB per 64-voice group); eight
+// voice slots of that do not fit beside the instrument pipeline's queues.  A V wave reads instead the fixed
+// slots of the NEXT segment one segment ahead and keeps them in registers (the packet may be pinned host memory:
+// the round trip hides under a segment's samples) ...
+__device__ __forceinline__ uint2 seg_event_fetch(const uint2 *evs, uint32_t seg, uint32_t groups, uint32_t group, uint32_t lane) {
+    uint2 e = make_uint2(0u, 0u);
+    if (lane < kVevCap) e = evs[((size_t)seg * groups + group) * kVevCap + lane];
+    return e;
+}
+// ... and at the segment start scatters them through its 64 slots, exactly as voice_event_of does (a crowded
+// segment's overflow run is a dependent second read here: slower, correct).
+__device__ __forceinline__ VoiceEv seg_event_take(uint2 e, const uint2 *evs_more, uint2 *slot, uint32_t lane, uint32_t me) {
+    slot[lane] = make_uint2(0u, 0u);
+    const uint32_t head = __builtin_amdgcn_readfirstlane(e.x);
+    if ((head >> 8) & VEV_MORE) {
+        const uint32_t cnt = head >> 16, first = __builtin_amdgcn_readfirstlane(e.y);
+        e = make_uint2(0u, 0u);
+        if (lane < cnt) e = evs_more[first + lane];
+    }
+    if (e.x >> 8) slot[e.x & 63u] = make_uint2(e.x >> 8, e.y);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint2 v = slot[me];
+    return VoiceEv{v.x, __uint_as_float(v.y)};
+}
+// A segment start from registers, what voice_envs_load does at a launch's start from the stored state: the flags
+// word from the live envelope modes, gprev and gate; the segment's gate events on it; both Env::begin.
+__device__ __forceinline__ void voice_envs_restart(VoiceEnvs &v, const VoiceEv &ev, const float *c, uint32_t cn, uint32_t ci) {
+    uint32_t flags0 = v.ea.mode | v.ef.mode << 3 | (uint32_t)v.gprev_a << 6 | (uint32_t)v.gprev_f << 7 | (uint32_t)v.gate << 8;
+    float xa0 = v.ea.x, xf0 = v.ef.x;
+    apply_gate_events(ev, flags0, xa0, xf0);
+    v.gate = (flags0 >> 8) & 1u;
+    v.gprev_a = (flags0 >> 6) & 1u;
+    v.gprev_f = (flags0 >> 7) & 1u;
+    v.ea.begin(v.gate, v.gprev_a, flags0 & 7u, xa0, c[VCC_ATK_D0A * cn + ci], c[VCC_ATK_TGT_A * cn + ci],
+               c[VCC_DEC_D0A * cn + ci], c[VCC_REL_D0A * cn + ci], c[VCC_SUS_A * cn + ci]);
+    v.ef.begin(v.gate, v.gprev_f, (flags0 >> 3) & 7u, xf0, c[VCC_ATK_D0F * cn + ci], c[VCC_ATK_TGT_F * cn + ci],
+               c[VCC_DEC_D0F * cn + ci], c[VCC_REL_D0F * cn + ci], c[VCC_SUS_F * cn + ci]);
+}
+
 // samples per hand-off between the roles: 8 (34 barrier steps per 256-frame block, pipeline fill
 // 2 of them) measured 2 % faster than 16 (18 steps) for the Svf voice and equal for the Moog
 // voice; 32 halves the workgroups per CU (96 KB of LDS each) and is 1.7x slower

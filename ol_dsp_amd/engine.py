@@ -250,6 +250,43 @@ class Engine:
             arr[k].ev.value = float(e[4]) if len(e) > 4 else 0.0
         check(self.lib.olfx_timed_events(self._h, arr, len(evs)), self._h)
 
+    @staticmethod
+    def make_timed_notes(frames, inst, type_, note):
+        """A prebuilt note array (numpy-vectorised) for timed_notes: frame / inst / note arrays (or scalars
+        broadcast against inst), type one of _lib.EV_* but SetFrequency."""
+        inst = np.asarray(inst, np.uint32).ravel()
+        rec = np.zeros(len(inst), dtype=[("frame", "<u4"), ("inst", "<u4"), ("type", "u1"), ("note", "u1"),
+                                         ("velocity", "u1"), ("pad", "u1")])
+        rec["frame"] = frames
+        rec["inst"] = inst
+        rec["type"] = type_
+        rec["note"] = note
+        rec["velocity"] = 100
+        assert ctypes.sizeof(_lib.TimedNote) == rec.dtype.itemsize
+        return rec
+
+    def timed_notes(self, events) -> None:
+        """Notes at a frame inside the coming blocks (the synth kinds and the drum kit; olfx_timed_notes): iterable
+        of (frame, inst, type, note), or an array from make_timed_notes().  frame counts from the first frame of the
+        next process() and is a multiple of 4; a note is routed to a voice when the engine reaches its frame, and a
+        note past the block stays pending."""
+        if isinstance(events, np.ndarray):
+            if len(events):
+                check(self.lib.olfx_timed_notes(self._h, events.ctypes.data_as(ctypes.POINTER(_lib.TimedNote)),
+                                                len(events)), self._h)
+            return
+        evs = list(events)
+        if not evs:
+            return
+        arr = (_lib.TimedNote * len(evs))()
+        for k, e in enumerate(evs):
+            arr[k].frame = int(e[0])
+            arr[k].ev.inst = int(e[1])
+            arr[k].ev.type = int(e[2])
+            arr[k].ev.note = int(e[3]) if len(e) > 3 else 0
+            arr[k].ev.velocity = 100
+        check(self.lib.olfx_timed_notes(self._h, arr, len(evs)), self._h)
+
     def update(self, first: int = 0, count: int = -1) -> None:
         """Update() of instances first..first+count with their current parameters."""
         count = self.n - first if count < 0 else count
