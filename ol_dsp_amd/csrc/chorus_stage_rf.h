@@ -24,8 +24,19 @@
 // each chunk) is addressed with wave-uniform slot numbers.  Frame k with delay d reads slots
 // kTail + k - (d - L) and the one below: 0 <= d - L <= kTail - 1 is what choose_lead checks (the
 // delay moves by < 10 samples in 256 frames at the fastest legal depth x rate; where the bound does
-// not hold for some lane, the wave halves the segment).  A segment's first chunk computes the kTail
-// old positions directly from the ring (psv_direct): one extra, shorter pitch pass per launch.
+// not hold for some lane, the wave halves the segment).
+//
+// Segment start.  The kTail old positions of a segment's first chunk come from a LEAD-IN chunk: the
+// fast path's phase A run once over the 16 positions w0 - L - 16 .. w0 - L - 1 (phasor 16 ps_inc
+// further back, plan and lines relative to write position w0 - 16), of which the last kTail are
+// kept.  It has no tap, no output, no ring store and no x patch: it reads x at positions <= w0 - 2,
+// all in the ring from earlier chunks or launches, and its lines are loaded fresh.  Its line
+// addresses do not depend on the segment's input, so they are issued along with the first input
+// loads; chunk 0 then finds its window one line on from the lead-in's, carries that line and loads
+// one new line per tap, issued ahead of the lead-in's arithmetic.  Where the two lines cannot cover
+// the lead-in's windows for every lane of the wave (a phasor wrap inside the 16 positions), the
+// wave computes the kTail positions straight from the ring instead (psv_direct, four at a time) and
+// loads chunk 0's windows fresh.
 //
 // Staleness, restated for the shifted time base.  As in v11 each chunk stores the NEXT chunk's
 // input x_{c+1} to the ring before it issues the next chunk's line loads, so a freshly loaded line
@@ -86,6 +97,12 @@ struct ChStageRF : ChStageL<false, COOP, false> {
     using B::started;
 
     uint32_t lead;            // L of the segment; ps_acc is the SHIFTED phasor (position wpos - L) meanwhile
+    Rsrc rNone;               // the x ring with no records: loads against it fetch nothing
+
+    __device__ __forceinline__ void init(const ChorusArgs &a, float *lds_region, uint32_t lane_, uint32_t inst0_) {
+        B::init(a, lds_region, lane_, inst0_);
+        rNone = rsrc(a.pitch_ring, 0);
+    }
 
     // Bounds of the chorus delay over the next len frames -> the segment's lead; false if the psv
     // window cannot hold the delay's excursion (the caller shortens the segment).  The delay is
@@ -142,9 +159,55 @@ struct ChStageRF : ChStageL<false, COOP, false> {
         return *(const float4 *)(region + (r & 1u) * kOutCh + (r >> 1) * 32u + (lane & 7u) * 4u);
     }
 
-    // First chunk of a segment (choose_lead has run): store its inputs, shift the phasor, compute
-    // the kTail positions below the chunk's own straight from the ring, load every window fresh.
+    // v11's phase A on the shifted time base, for the positions K0 .. 15 of the 16 whose windows p
+    // plans (acc: the phasor of position K0, advanced past the last on return): position index k
+    // reads slot k - L - d - s (s relative to the first write position)
+    template <int K0>
+    __device__ __forceinline__ void phase_a(uint64_t &acc, const PlanL &p, const float *wP0, const float *wP1,
+                                            float (&psv)[kChunk]) const {
+        static_assert(K0 % 2 == 0, "frame pairs");
+        const int L = (int)lead;
+        const int chA = (int)ch - L - p.sA, chB = (int)ch - L - p.sB;
+        float gA0 = 0.f, gA1 = 0.f, gB0 = 0.f, gB1 = 0.f, fA0 = 0.f, fA1 = 0.f, fB0 = 0.f, fB1 = 0.f;
+        int rA0 = 0, rA1 = 0, rB0 = 0, rB1 = 0;
+#pragma unroll
+        for (int k = K0; k < kChunk; ++k) {
+            if ((k & 1) == 0) {
+                const uint64_t pa = acc + (ch ? ps_inc : 0ull);
+                const uint32_t ph = hi32(pa);
+                float m_gA, m_gB;
+                win_gains(unit24(ph), m_gA, m_gB);
+                gA0 = pair_even(m_gA); gA1 = pair_odd(m_gA);
+                gB0 = pair_even(m_gB); gB1 = pair_odd(m_gB);
+                uint32_t di; float fr;
+                pitch_split(ph, wi, wf, pmaxu, di, fr);
+                const int ra = chA - (int)di;
+                rA0 = pair_even_i(ra); rA1 = pair_odd_i(ra);
+                fA0 = pair_even(fr); fA1 = pair_odd(fr);
+                pitch_split(ph + 0x80000000u, wi, wf, pmaxu, di, fr);
+                const int rb = chB - (int)di;
+                rB0 = pair_even_i(rb); rB1 = pair_odd_i(rb);
+                fB0 = pair_even(fr); fB1 = pair_odd(fr);
+            }
+            acc += ps_inc;
+            const bool odd = k & 1;
+            const float *qA = wP0 + (k & ~1) * kRow + (odd ? rA1 : rA0) * kRow;
+            const float *qB = wP1 + (k & ~1) * kRow + (odd ? rB1 : rB0) * kRow;
+            const float tA = lerp_pair(qA[0], qA[-kRow], odd ? fA1 : fA0);
+            const float tB = lerp_pair(qB[0], qB[-kRow], odd ? fB1 : fB0);
+            psv[k] = xfade(tB, odd ? gB1 : gB0, tA, odd ? gA1 : gA0);
+        }
+    }
+
+    // First chunk of a segment (choose_lead has run; the caller has issued the loads of its inputs):
+    // shift the phasor, issue the lead-in's line loads, store the inputs, then the kTail positions
+    // below the chunk's own -- the lead-in's phase A under chunk 0's line loads, or the direct pass.
     __device__ __forceinline__ void begin_segment(float (&x)[kChunk], int C, const float4 (&xq)[4]) {
+        ps_acc -= (uint64_t)lead * ps_inc;
+        // the lead-in: positions wpos - L - 16 .. wpos - L - 1 as a chunk written at wpos - 16
+        const PlanL li = plan_rf(ps_acc - (uint64_t)kChunk * ps_inc, kChunk);
+        const bool leadin = __all(li.okA && li.okB);
+        if (leadin) B::template load_lines<1>(li, wpos - (uint32_t)kChunk, true);
         if (COOP) {
             B::stage_rows(xq);
             B::coop_store(true, 0, wpos, C);
@@ -153,23 +216,37 @@ struct ChStageRF : ChStageL<false, COOP, false> {
             B::stage_run(x, 0);
             B::coop_store(true, 0, wpos, C);
         }
-        ps_acc -= (uint64_t)lead * ps_inc;
         float *wV = region + kPsvWin + lane;
-        const uint32_t pb = B::own_pb();
-        // (rolled by four: the whole pass in flight at once costs registers the chunk loop then spills)
+        if (leadin) {
+            // (the input staging above lies under the pitch windows: staged after it is read)
+            B::template stage_tap<1, 0>();
+            B::template stage_tap<1, 1>();
+        } else {
+            const uint32_t pb = B::own_pb();
+            // (rolled by four: the whole pass in flight at once costs registers the chunk loop then spills)
 #pragma unroll 1
-        for (int m0 = 0; m0 < kTail; m0 += 4) {
-            float tv[4];
+            for (int m0 = 0; m0 < kTail; m0 += 4) {
+                float tv[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                tv[u] = psv_direct(rP, pb, pmask, ps_acc - (uint64_t)(kTail - m0 - u) * ps_inc,
-                                   wpos - lead - (uint32_t)(kTail - m0 - u), wi, wf, pmaxu);
+                for (int u = 0; u < 4; ++u)
+                    tv[u] = psv_direct(rP, pb, pmask, ps_acc - (uint64_t)(kTail - m0 - u) * ps_inc,
+                                       wpos - lead - (uint32_t)(kTail - m0 - u), wi, wf, pmaxu);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) wV[(m0 + u) * kRow] = tv[u];
+                for (int u = 0; u < 4; ++u) wV[(m0 + u) * kRow] = tv[u];
+            }
         }
+        // chunk 0's lines: after the lead-in it carries the lead-in's upper line (set 1) where its
+        // window lies one line on, and the loads see the inputs stored above (same wave, issue order)
         pl = plan_rf(ps_acc, C);
         started = false;
-        B::template load_lines<0>(pl, wpos, true);
+        B::template load_lines<0>(pl, wpos, !leadin);
+        if (leadin) {
+            float psv[kChunk];
+            uint64_t acc = ps_acc - (uint64_t)kTail * ps_inc;
+            phase_a<kChunk - kTail>(acc, li, region + 0 * kSlots * kRow + lane, region + 1 * kSlots * kRow + lane, psv);
+#pragma unroll
+            for (int m = 0; m < kTail; ++m) wV[m * kRow] = psv[kChunk - kTail + m];
+        }
     }
     // the phasor back on the stream's own time base (the next segment's lead, or finish())
     __device__ __forceinline__ void end_segment() { ps_acc += (uint64_t)lead * ps_inc; }
@@ -190,7 +267,13 @@ struct ChStageRF : ChStageL<false, COOP, false> {
             B::coop_store(true, 0, w0 + (uint32_t)C, Cn);
         }
         pl = plan_rf(ps0 + (uint64_t)C * ps_inc, Cn > 0 ? Cn : 4);
+        // after a segment's last chunk nobody reads the lines: the same instructions run against an
+        // empty buffer (every load out of range: zeros, no memory access), so the chunk body keeps
+        // one shape -- a load under a branch would cost the steady chunks their waits
+        const Rsrc ring = rP;
+        rP = Cn > 0 ? ring : rNone;
         B::template load_lines<PAR ^ 1>(pl, w0 + (uint32_t)C, false);
+        rP = ring;
     }
 
     // One chunk of C frames with input x; xn / Cn / prefetch / xq as in ChStageL::chunk.  Order:
@@ -244,38 +327,8 @@ struct ChStageRF : ChStageL<false, COOP, false> {
 
         const bool fast = C == kChunk && __all(cur.okA && cur.okB);
         if (fast) {
-            // A. v11's phase A on the shifted time base: position index k reads slot
-            //    k - L - d - s (s relative to w0)
-            const int chA = (int)ch - L - cur.sA, chB = (int)ch - L - cur.sB;
-            float gA0 = 0.f, gA1 = 0.f, gB0 = 0.f, gB1 = 0.f, fA0 = 0.f, fA1 = 0.f, fB0 = 0.f, fB1 = 0.f;
-            int rA0 = 0, rA1 = 0, rB0 = 0, rB1 = 0;
-#pragma unroll
-            for (int k = 0; k < kChunk; ++k) {
-                if ((k & 1) == 0) {
-                    const uint64_t pa = ps_acc + (ch ? ps_inc : 0ull);
-                    const uint32_t ph = hi32(pa);
-                    float m_gA, m_gB;
-                    win_gains(unit24(ph), m_gA, m_gB);
-                    gA0 = pair_even(m_gA); gA1 = pair_odd(m_gA);
-                    gB0 = pair_even(m_gB); gB1 = pair_odd(m_gB);
-                    uint32_t di; float fr;
-                    pitch_split(ph, wi, wf, pmaxu, di, fr);
-                    const int ra = chA - (int)di;
-                    rA0 = pair_even_i(ra); rA1 = pair_odd_i(ra);
-                    fA0 = pair_even(fr); fA1 = pair_odd(fr);
-                    pitch_split(ph + 0x80000000u, wi, wf, pmaxu, di, fr);
-                    const int rb = chB - (int)di;
-                    rB0 = pair_even_i(rb); rB1 = pair_odd_i(rb);
-                    fB0 = pair_even(fr); fB1 = pair_odd(fr);
-                }
-                ps_acc += ps_inc;
-                const bool odd = k & 1;
-                const float *qA = wP0 + (k & ~1) * kRow + (odd ? rA1 : rA0) * kRow;
-                const float *qB = wP1 + (k & ~1) * kRow + (odd ? rB1 : rB0) * kRow;
-                const float tA = lerp_pair(qA[0], qA[-kRow], odd ? fA1 : fA0);
-                const float tB = lerp_pair(qB[0], qB[-kRow], odd ? fB1 : fB0);
-                psv[k] = xfade(tB, odd ? gB1 : gB0, tA, odd ? gA1 : gA0);
-            }
+            // A. v11's phase A on the shifted time base
+            phase_a<0>(ps_acc, cur, wP0, wP1, psv);
         } else {
             // generic chunk: the positions its frames can read (index < C), straight from the ring
             const uint32_t pb = B::own_pb();

@@ -6,6 +6,7 @@
 //   r3w1     : R = 3, W = 1 (chorus 34 : 24 is ~ r3w2; reverb 117 : 58 is ~ r2w1)
 //   taps     : the reverb's shape -- per 4-frame step a wave reads 12 groups of 1 KB from 12
 //              streams 1 MB apart and writes 6 (R : W = 2 : 1), 1024 waves in flight
+//   chorus_shape, chorus_shape_rf : the chorus kernels' own shapes (below)
 // Build: hipcc --offload-arch=gfx950 -O3 -o tools/bw_probe tools/bw_probe.hip ; run: tools/bw_probe
 #include <hip/hip_runtime.h>
 
@@ -106,6 +107,47 @@ __global__ __launch_bounds__(64) void chorus_shape(const float4 *__restrict__ in
     if (acc == 12345.f) *sink = acc;
 }
 
+// the ring-free chorus's access shape (chorus_block_rf1): one 2,048-position stereo ring per instance
+// (128 lines of 128 B); per 16-frame chunk and instance two tap lines read from it and one line
+// written to it, the input and output rows as in chorus_shape<32>: 24 + 16 B per frame.  No arithmetic.
+__global__ __launch_bounds__(64) void chorus_shape_rf(const float4 *__restrict__ in, float4 *__restrict__ out,
+                                                      float4 *__restrict__ ring, uint32_t n, uint32_t chunks,
+                                                      float *sink) {
+    const uint32_t lane = threadIdx.x, inst0 = blockIdx.x * 32u;
+    const uint32_t piece = lane & 7u;
+    float acc = 0.f;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t j = inst0 + 8u * q + (lane >> 3);
+            const uint32_t h = j * 2654435761u;           // per-instance tap offsets
+            const uint32_t pA = (c + 1u + ((h >> 8) & 63u)) & 127u, pB = (pA + 3u + (h & 15u)) & 127u;
+            const float4 a = ring[((size_t)j * 128u + pA) * 8u + piece];
+            const float4 b = ring[((size_t)j * 128u + pB) * 8u + piece];
+            v.x += a.x + b.x; v.y += a.y + b.y;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t r = 8u * q + lane / 8u, f = 16u * c + (r >> 1), ch = r & 1u;
+            const float4 x = in[(((size_t)ch * 16u * chunks + f) * n + inst0) / 4u + lane % 8u];
+            v.z += x.x; v.w += x.y;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t j = inst0 + 8u * q + (lane >> 3);
+            ring[((size_t)j * 128u + (c & 127u)) * 8u + piece] = v;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t r = 8u * q + lane / 8u, f = 16u * c + (r >> 1), ch = r & 1u;
+            out[(((size_t)ch * 16u * chunks + f) * n + inst0) / 4u + lane % 8u] = v;
+        }
+        acc += v.x;
+    }
+    if (acc == 12345.f) *sink = acc;
+}
+
 int main() {
     const size_t bytes = (size_t)2 << 30, n = bytes / 16;
     float4 *buf[5];
@@ -171,6 +213,20 @@ int main() {
         shape(chorus_shape<32>, 32, "32 instances per wave: 2 waves/SIMD");
         shape(chorus_shape<16>, 16, "16 instances per wave: 4 waves/SIMD");
         shape(chorus_shape<32>, 32, "32 instances per wave: 2 waves/SIMD, again");
+        // the ring-free shape: the 2,048-position ring alone (cr holds exactly n of them)
+        for (int rep = 0; rep < 2; ++rep) {
+            for (int w = 0; w < 3; ++w) hipLaunchKernelGGL(chorus_shape_rf, dim3(n / 32), dim3(64), 0, 0, in, out, cr, n, chunks, sink);
+            CHK(hipEventRecord(e0));
+            const int it = 20;
+            for (int w = 0; w < it; ++w) hipLaunchKernelGGL(chorus_shape_rf, dim3(n / 32), dim3(64), 0, 0, in, out, cr, n, chunks, sink);
+            CHK(hipEventRecord(e1));
+            CHK(hipEventSynchronize(e1));
+            float ms = 0.f;
+            CHK(hipEventElapsedTime(&ms, e0, e1));
+            const double gbs = (double)n * F * 40.0 * it / (ms * 1e-3) / 1e9;
+            std::printf("chorus_shape_rf R24 W16 B/frame (32 instances per wave, 65,536 instances)  %8.1f GB/s  %.3f of 8000  %.4f ms per block\n",
+                        gbs, gbs / 8000.0, ms / it);
+        }
     }
     return 0;
 }
