@@ -59,6 +59,10 @@ def run_engine(kind, script, n, voices, cuda, timed=True, io="device", e=None):
             e.set_params(0, step[1])
         elif op == "events":
             e.note_events(step[1])
+        elif op == "set":
+            e.set_param(step[1], step[2], step[3])
+        elif op == "control":
+            e.control(step[1])
         else:
             raise ValueError(op)
     return (np.concatenate(out, 1) if out else None), tables, e
