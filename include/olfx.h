@@ -561,6 +561,41 @@ int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n);
    type > GATE_OFF; a drum kit: type > NOTE_ON).  OLFX_E_KIND: the three voice kinds (olfx_timed_events).
    OLFX_E_STATE: effect and meter kinds. */
 int olfx_timed_notes(olfx_engine *e, const olfx_timed_note *ev, uint32_t n);
+/* Parameter and control changes at a frame inside the block (OLFX_KIND_VOICE, OLFX_KIND_VOICE_MOOG,
+   OLFX_KIND_VOICE_SAMPLE).  A parameter record is olfx_set_param(inst, field, value) at its frame, a control
+   record olfx_control(&ev, 1) at its frame: UpdateConfig + Update() of that voice there, as olfx_set_param
+   implies it.  A control that maps to OLFX_FIELD_UPDATE_ONLY is Update() at its frame (the voice becomes
+   configured there); a control the reference ignores is skipped.  One olfx_process(N) computes, bit for bit in
+   output and stored state, what one process call per distinct time below N computes -- a time being the frame
+   of a timed event or of a timed parameter record -- when before each call that time's parameter records are
+   applied by olfx_set_param / olfx_control in queueing order (both calls share one order) and that time's
+   events are then queued by olfx_voice_events.  At a frame, parameter changes precede events whatever the
+   queueing order: the block-boundary rule.
+     - a record at frame 0 is exactly olfx_set_param / olfx_control now;
+     - a record at or past N stays pending with its frame reduced by N; one whose frame becomes 0 is applied as
+       that olfx_process returns, ahead of anything set afterwards; olfx_reset drops pending records;
+     - olfx_get_param reads the value as of the frames processed so far, plus the frame-0 writes made since, and
+       olfx_set_member's OLFX_E_STATE rule is judged on that same state;
+     - olfx_set_params, olfx_set_param_list, olfx_control, olfx_update, olfx_sample_voices and olfx_sample_bank
+       keep landing at the block boundary, before every pending timed record;
+     - parameter times and event times share the 16 segments of a launch, and a launch carries at most n_inst
+       changed-voice records; a call with more runs as several launches.
+   OLFX_E_ARG (nothing is queued, the shadow is untouched): null with n > 0, a frame that is no multiple of 4 or
+   not below 2^31, inst or field out of range, a value olfx_set_param refuses, a control record olfx_control
+   refuses.  OLFX_E_KIND: every kind but the three voice kinds. */
+typedef struct olfx_timed_param {
+    uint32_t frame;         /* multiple of 4, below 2^31 */
+    uint32_t inst;
+    uint32_t field;
+    float    value;
+} olfx_timed_param;
+/* (a struct tag only: the record shares its name with the call, which a typedef name could not) */
+struct olfx_timed_control {
+    uint32_t frame;         /* multiple of 4, below 2^31 */
+    olfx_control_event ev;
+};
+int olfx_timed_params(olfx_engine *e, const olfx_timed_param *rec, uint32_t n);
+int olfx_timed_control(olfx_engine *e, const struct olfx_timed_control *rec, uint32_t n);
 /* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF / OLFX_KIND_DRUMKIT: Playing() of the `voices` voices of instrument (kit) inst,
    as of the calls made so far (with timed notes: as of the frames processed so far). */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);

@@ -126,6 +126,22 @@ class ControlEvent(ctypes.Structure):
     ]
 
 
+class TimedParam(ctypes.Structure):
+    _fields_ = [
+        ("frame", ctypes.c_uint32),
+        ("inst", ctypes.c_uint32),
+        ("field", ctypes.c_uint32),
+        ("value", ctypes.c_float),
+    ]
+
+
+class TimedControl(ctypes.Structure):
+    _fields_ = [
+        ("frame", ctypes.c_uint32),
+        ("ev", ControlEvent),
+    ]
+
+
 class SampleVoice(ctypes.Structure):
     _fields_ = [
         ("inst", ctypes.c_uint32),
@@ -184,6 +200,8 @@ SIGNATURES = {
     "olfx_voice_events": (ctypes.c_int, [_P, ctypes.POINTER(VoiceEvent), _U32]),
     "olfx_timed_events": (ctypes.c_int, [_P, ctypes.POINTER(TimedEvent), _U32]),
     "olfx_timed_notes": (ctypes.c_int, [_P, ctypes.POINTER(TimedNote), _U32]),
+    "olfx_timed_params": (ctypes.c_int, [_P, ctypes.POINTER(TimedParam), _U32]),
+    "olfx_timed_control": (ctypes.c_int, [_P, ctypes.POINTER(TimedControl), _U32]),
     "olfx_update": (ctypes.c_int, [_P, _U32, _U32]),
     "olfx_control_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_F)]),

@@ -401,6 +401,7 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     }
     lap(3);
     if (evs) hs.write_events(sl.h + pl.o_ev);
+    if (pl.n_tc) hs.write_timed_coefs(pl, sl.h);
     if (copy) {
         // the copy stream waits for nothing on the device: the host made sure above that the slot's
         // previous readers are done (a device-side wait there serialised the copy behind them)
@@ -438,6 +439,11 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
             va->n_seg = (uint32_t)pl.n_seg;
             va->n_chunks = hs.n_chunks(span, kVoiceChunk);
             va->seg = dev + pl.o_seg;
+            if (pl.n_tc) {                // timed parameters: the segments' coefficient records
+                va->tc_base = dev + pl.o_tcb;
+                va->tc = dev + pl.o_tc;
+                va->tc_n = (uint32_t)pl.n_tc;
+            }
         }
     }
     lap(5);
@@ -621,6 +627,9 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
         a.n_seg = ev.n_seg;
         a.n_chunks = ev.n_chunks;
         a.seg = ev.seg;
+        a.tc_base = ev.tc_base;
+        a.tc = ev.tc;
+        a.tc_n = ev.tc_n;
         r = e->kind == OLFX_KIND_VOICE_SAMPLE ? launch_sampler(a, s) : launch_voice(a, s);
         break;
     }
@@ -906,7 +915,8 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     // say -- pays a pinned / device allocation: the small ones at the copy threshold, the big ones
     // for the largest packet this engine can produce (up to 256 MiB each; larger on first need)
     const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev(),
-                                               std::max(host::max_segments(kind), host::max_note_segments(kind)));
+                                               std::max(host::max_segments(kind), host::max_note_segments(kind))) +
+                        host::max_timed_param_words(kind, n_inst);
     for (olfx_engine::Slot &sl : e->slot)
         if (!rc) rc = grow_slot(e, sl, olfx_engine::kCopyBytes / 4, false);
     if (maxw * 4 >= e->copy_bytes && maxw * 4 <= ((size_t)256 << 20))
@@ -1004,6 +1014,14 @@ int olfx_timed_events(olfx_engine *e, const olfx_timed_event *ev, uint32_t n) {
 
 int olfx_timed_notes(olfx_engine *e, const olfx_timed_note *ev, uint32_t n) {
     return e ? e->report(e->hs.timed_notes(ev, n)) : OLFX_E_ARG;
+}
+
+int olfx_timed_params(olfx_engine *e, const olfx_timed_param *rec, uint32_t n) {
+    return e ? e->report(e->hs.timed_params(rec, n)) : OLFX_E_ARG;
+}
+
+int olfx_timed_control(olfx_engine *e, const struct olfx_timed_control *rec, uint32_t n) {
+    return e ? e->report(e->hs.timed_control(rec, n)) : OLFX_E_ARG;
 }
 
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing) {

@@ -581,7 +581,11 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
     for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
     for (uint32_t j = 0; j < kd->nparts; ++j) {
         const Component &c = kComponents[kd->parts[j].comp];
-        c.derive(p + kd->parts[j].field0, *this, i, w);
+        // (a voice whose last timed record still stands: those words, fold_segments derived them)
+        if (!tc_cache.empty() && kd->parts[j].comp == CP_VOICE && tc_cache_of[i] >= 0)
+            std::memcpy(w, tc_cache.data() + tc_cache_of[i], (size_t)VCC_N * 4);
+        else
+            c.derive(p + kd->parts[j].field0, *this, i, w);
         w += c.words;
     }
 }
@@ -634,6 +638,13 @@ void Shadow::reset() {
     pre_changed = true;
     events.clear();
     timed.clear();
+    tparams.clear();
+    tc_inst.clear();
+    pre_valid = false;
+    tc_fresh = false;
+    tc_cache_of.assign(kd->instances == KindDesc::VOICES ? n : 0u, -1);
+    tc_cache.clear();
+    tc_cached.clear();
     ev_slot.assign(n_ev(), -1);
     playing.assign((size_t)voices * n, 0);
     dirty_list.clear();
@@ -645,6 +656,8 @@ void Shadow::reset() {
 }
 
 void Shadow::mark_dirty(uint32_t first, uint32_t count) {
+    if (!tc_cache.empty())                                // whatever is written now, a kept timed record is stale
+        for (uint32_t k = first; k < first + count; ++k) tc_cache_of[k] = -1;
     for (uint32_t k = first; k < first + count; ++k)
         if (!dirty_mark[k]) {
             dirty_mark[k] = 1;
@@ -1129,20 +1142,116 @@ int Shadow::timed_notes(const olfx_timed_note *ev, uint32_t count) {
     return OLFX_OK;
 }
 
-uint32_t Shadow::span(uint32_t n_frames) const {
-    uint32_t segs = 1, last = 0;                          // segment 0 starts at frame 0, events or none
-    for (const olfx_timed_event &t : timed) {
-        if (t.frame >= n_frames) break;
-        if (t.frame != last) {
-            if (segs == kSegCap) return t.frame;
-            ++segs;
-            last = t.frame;
+// Timed parameter and control changes of the voice kinds.  A record at frame 0 is olfx_set_param / olfx_control
+// now; a later one stays pending until the engine reaches its frame (fold_segments, advance).
+void Shadow::apply_param(const olfx_timed_param &r, bool mark) {
+    if (r.field != OLFX_FIELD_UPDATE_ONLY) store_param(r.field, r.inst, r.value);
+    configured[r.inst] = 1;                               // a voice kind: every write implies Update()
+    if (mark) mark_dirty(r.inst, 1);
+}
+
+int Shadow::queue_params(const olfx_timed_param *rec, size_t count) {
+    const size_t old = tparams.size();
+    for (size_t k = 0; k < count; ++k) {
+        if (rec[k].frame == 0u) apply_param(rec[k], true);
+        else tparams.push_back(rec[k]);
+    }
+    const auto by_frame = [](const olfx_timed_param &x, const olfx_timed_param &y) { return x.frame < y.frame; };
+    std::stable_sort(tparams.begin() + (ptrdiff_t)old, tparams.end(), by_frame);
+    std::inplace_merge(tparams.begin(), tparams.begin() + (ptrdiff_t)old, tparams.end(), by_frame);
+    return OLFX_OK;
+}
+
+int Shadow::timed_params(const olfx_timed_param *rec, uint32_t count) {
+    if (kd->instances != KindDesc::VOICES) return fail(OLFX_E_KIND, "olfx_timed_params: the three voice kinds only");
+    if (count && !rec) return fail(OLFX_E_ARG, "olfx_timed_params: null records");
+    for (uint32_t k = 0; k < count; ++k) {
+        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_params: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (rec[k].inst >= n || rec[k].field >= n_params) return fail(OLFX_E_ARG, "olfx_timed_params: record %u out of range", k);
+        if (const char *why = bad_value(rec[k].field, rec[k].value)) return fail(OLFX_E_ARG, "olfx_timed_params: record %u: %s", k, why);
+    }
+    return queue_params(rec, count);
+}
+
+int Shadow::timed_control(const struct olfx_timed_control *rec, uint32_t count) {
+    if (kd->instances != KindDesc::VOICES) return fail(OLFX_E_KIND, "olfx_timed_control: the three voice kinds only");
+    if (count && !rec) return fail(OLFX_E_ARG, "olfx_timed_control: null records");
+    // a voice's controls map the same at every frame (no topology): mapped here, held as parameter records
+    std::vector<olfx_timed_param> mapped;
+    mapped.reserve(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_control_event &ev = rec[k].ev;
+        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_control: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (ev.inst >= n) return fail(OLFX_E_ARG, "olfx_timed_control: record %u: instance out of range", k);
+        uint32_t fields[2];
+        float vals[2];
+        const int hits = route_control(*kd, 0u, ev.control, ev.source, ev.value, fields, vals);
+        if (hits < 0) return fail(OLFX_E_ARG, "olfx_timed_control: record %u", k);
+        for (int h = 0; h < hits; ++h) {                  // (none: a control the reference ignores)
+            if (fields[h] != OLFX_FIELD_UPDATE_ONLY)
+                if (const char *why = bad_value(fields[h], vals[h])) return fail(OLFX_E_ARG, "olfx_timed_control: record %u: %s", k, why);
+            mapped.push_back(olfx_timed_param{rec[k].frame, ev.inst, fields[h], vals[h]});
         }
     }
-    return n_frames;
+    return queue_params(mapped.data(), mapped.size());
+}
+
+uint32_t Shadow::span(uint32_t n_frames) const {
+    uint32_t segs = 1, last = 0;                          // segment 0 starts at frame 0, events or none
+    if (!has_timed_params(n_frames)) {
+        for (const olfx_timed_event &t : timed) {
+            if (t.frame >= n_frames) break;
+            if (t.frame != last) {
+                if (segs == kSegCap) return t.frame;
+                ++segs;
+                last = t.frame;
+            }
+        }
+        return n_frames;
+    }
+    // event times and parameter times in one ascending walk (all are past frame 0); a parameter time adds a
+    // coefficient record per voice it changes, and the launch holds n of them
+    const uint32_t none = 0xFFFFFFFFu;
+    size_t ke = 0, kp = 0, recs = 0;
+    // (n records or fewer below the block: the record bound cannot bite, whatever voices they name)
+    size_t below = 0;
+    while (below < tparams.size() && tparams[below].frame < n_frames) ++below;
+    const bool count_voices = below > n;
+    std::vector<uint32_t> at;
+    for (;;) {
+        const uint32_t te = ke < timed.size() ? timed[ke].frame : none, tp = kp < tparams.size() ? tparams[kp].frame : none;
+        const uint32_t t = te < tp ? te : tp;
+        if (t >= n_frames) return n_frames;
+        if (segs == kSegCap) return t;
+        if (tp == t && !count_voices) {
+            while (kp < tparams.size() && tparams[kp].frame == t) ++kp;
+        } else if (tp == t) {
+            at.clear();
+            for (; kp < tparams.size() && tparams[kp].frame == t; ++kp) at.push_back(tparams[kp].inst);
+            std::sort(at.begin(), at.end());
+            const size_t c = (size_t)(std::unique(at.begin(), at.end()) - at.begin());
+            if (recs + c > n) return t;                   // (never the first time: c <= n)
+            recs += c;
+        }
+        while (ke < timed.size() && timed[ke].frame == t) ++ke;
+        ++segs;
+    }
 }
 
 void Shadow::advance(uint32_t span_) {
+    // parameter records first: at a frame they precede the events, and one that reaches frame 0 lands now,
+    // ahead of anything set from now on
+    size_t q = 0;
+    for (olfx_timed_param &r : tparams) {
+        r.frame = r.frame > span_ ? r.frame - span_ : 0u;
+        if (!r.frame) {
+            apply_param(r, true);
+            ++q;
+        }
+    }
+    tparams.erase(tparams.begin(), tparams.begin() + (ptrdiff_t)q);
     size_t k = 0;
     for (olfx_timed_event &t : timed) {
         t.frame = t.frame > span_ ? t.frame - span_ : 0u;
@@ -1298,7 +1407,56 @@ void Shadow::fold_events() {
 }
 
 // Timed events: every segment folds on its own, as the queue of a block that started at its frame would.
+// Timed parameters: a time's records are applied to the shadow here, in queueing order and ahead of that time's
+// events, and every voice they touch gets one coefficient record for the segment (derive_voice on the shadow as
+// that time leaves it) and VEV_COEF in its folded record.  The dirty instances' frame-0 records are derived
+// first (pre_words): fill_records runs after this fold and would see the later values.
 void Shadow::fold_segments(uint32_t span_) {
+    tc_inst.clear();
+    tc_words.clear();
+    tc_first.assign(1, 0u);
+    pre_valid = false;
+    tc_fresh = true;
+    if (has_timed_params(span_)) {
+        const size_t m = dirty_list.size(), W = kd->words;
+        pre_words.resize(m * W);
+        for (size_t r = 0; r < m; ++r) derive_record(m == n ? (uint32_t)r : dirty_list[r], pre_words.data() + r * W);
+        pre_valid = true;
+        fold_events();                                    // segment 0: the frame-0 queue
+        tc_first.push_back(0u);
+        const uint32_t none = 0xFFFFFFFFu;
+        size_t k = 0, q = 0;
+        std::vector<uint32_t> at;
+        for (;;) {
+            const uint32_t te = k < timed.size() ? timed[k].frame : none, tp = q < tparams.size() ? tparams[q].frame : none;
+            const uint32_t t = te < tp ? te : tp;
+            if (t >= span_) break;
+            seg_frame.push_back(t);
+            at.clear();
+            for (; q < tparams.size() && tparams[q].frame == t; ++q) {
+                apply_param(tparams[q], false);
+                at.push_back(tparams[q].inst);
+            }
+            if (!std::is_sorted(at.begin(), at.end())) std::sort(at.begin(), at.end());
+            at.erase(std::unique(at.begin(), at.end()), at.end());
+            for (const uint32_t v : at) {
+                float p[OLFX_VC_NPARAMS];
+                for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) p[f] = params[(size_t)(kd->voice0 + f) * n + v];
+                tc_words.resize(tc_words.size() + VCC_N);
+                derive_voice(p, configured[v] != 0, kd->moog, sr, tc_words.data() + tc_words.size() - VCC_N);
+                tc_inst.push_back(v);
+            }
+            size_t k1 = k;
+            while (k1 < timed.size() && timed[k1].frame == t) ++k1;
+            fold_one(k1 > k ? &timed[k].ev : nullptr, k1 - k, sizeof(olfx_timed_event), at.data(), at.size());
+            seg_first.push_back((uint32_t)folded.size());
+            tc_first.push_back((uint32_t)tc_inst.size());
+            k = k1;
+        }
+        timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+        tparams.erase(tparams.begin(), tparams.begin() + (ptrdiff_t)q);
+        return;
+    }
     fold_events();                                        // segment 0: the frame-0 queue
     size_t k = 0;
     while (k < timed.size() && timed[k].frame < span_) {
@@ -1319,9 +1477,13 @@ void Shadow::fold_segments(uint32_t span_) {
 }
 
 // `count` events `stride` bytes apart
-void Shadow::fold_one(const olfx_voice_event *evs, size_t count, size_t stride) {
+void Shadow::fold_one(const olfx_voice_event *evs, size_t count, size_t stride, const uint32_t *coef, size_t n_coef) {
     const uint32_t seek = kd->has_sample ? (uint32_t)VEV_SEEK : 0u;
     const size_t first = folded.size();
+    for (size_t c = 0; c < n_coef; ++c) {                 // (distinct voices) the events below join these records
+        ev_slot[coef[c]] = (int32_t)folded.size();
+        folded.push_back(Folded{coef[c], VEV_COEF, 0u, 0u});
+    }
     for (size_t e = 0; e < count; ++e) {
         const olfx_voice_event &ev = *reinterpret_cast<const olfx_voice_event *>(reinterpret_cast<const char *>(evs) + e * stride);
         int32_t &k = ev_slot[ev.inst];
@@ -1393,7 +1555,7 @@ void Shadow::write_events(uint32_t *fix) {
 }
 
 PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev, size_t m2, uint32_t W2,
-                       uint32_t n_seg) {
+                       uint32_t n_seg, size_t n_tc) {
     PacketPlan pl;
     pl.dense = m == n;                                   // every instance: no instance list
     pl.o_inst = 0;
@@ -1411,7 +1573,33 @@ PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_mo
         pl.o_seg = pl.words;
         pl.words += (pl.n_seg + 1u) & ~(size_t)1u;
     }
+    if (evs && pl.n_seg > 1 && n_tc) {                    // timed parameters: the base table, the records
+        pl.n_tc = n_tc;
+        pl.o_tcb = up4(pl.words);
+        pl.o_tc = up4(pl.o_tcb + pl.n_seg * (size_t)(((n_ev ? n_ev : n) + 63u) / 64u));
+        pl.words = pl.o_tc + (size_t)VCC_N * n_tc;
+    }
     return pl;
+}
+
+size_t max_timed_param_words(int kind, uint32_t n) {
+    if (kind_desc(kind).instances != KindDesc::VOICES) return 0;
+    // the section's alignment (up to 3 words), the base table of a full launch rounded up to the records', n records
+    return 3 + up4((size_t)kSegCap * ((n + 63u) / 64u)) + (size_t)VCC_N * n;
+}
+
+void Shadow::write_timed_coefs(const PacketPlan &pl, uint32_t *buf) const {
+    const size_t groups = (n_ev() + 63u) / 64u, T = tc_inst.size();
+    uint32_t *base = buf + pl.o_tcb, *rec = buf + pl.o_tc;
+    for (size_t s = 0; s + 1 < tc_first.size(); ++s) {
+        size_t r = tc_first[s];                           // ascending voices: group g's run starts where g - 1's ends
+        for (size_t g = 0; g < groups; ++g) {
+            base[s * groups + g] = (uint32_t)r;
+            while (r < tc_first[s + 1] && (tc_inst[r] >> 6) == g) ++r;
+        }
+    }
+    for (size_t r = 0; r < T; ++r)
+        for (uint32_t w = 0; w < VCC_N; ++w) rec[(size_t)w * T + r] = tc_words[r * VCC_N + w];
 }
 
 size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev, uint32_t n_seg) {
@@ -1449,7 +1637,8 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     for (size_t r = 0; r < m; ++r) {
         const uint32_t i = pl.dense ? (uint32_t)r : dirty_list[r];
         if (!pl.dense) buf[pl.o_inst + r] = i;
-        derive_record(i, h_words.data());
+        if (pre_valid) std::memcpy(h_words.data(), pre_words.data() + r * W, (size_t)W * 4);   // frame 0's (fold_segments)
+        else derive_record(i, h_words.data());
         if (kind == OLFX_KIND_CHORUS)
             for (uint32_t k = 0; k < 4; ++k) {
                 uint32_t &sent = pitch_sent[(size_t)k * n + i];
@@ -1460,6 +1649,24 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     }
     for (const uint32_t i : dirty_list) dirty_mark[i] = 0;
     dirty_list.clear();
+    // the voices the launch's timed records change stay dirty: the device arrays get their last record ahead of
+    // the next launch (the kernels never write the coefficient arrays)
+    pre_valid = false;
+    if (!tc_cache.empty()) {                              // the previous launch's voices alone: nothing else is set
+        for (const uint32_t i : tc_cached) tc_cache_of[i] = -1;
+        tc_cached.clear();
+        tc_cache.clear();
+    }
+    // (once per fold: a later packet without a fold of its own must not see this launch's records again)
+    for (size_t r = 0; tc_fresh && r < tc_inst.size(); ++r) {     // in segment order: a voice's last record stays
+        mark_dirty(tc_inst[r], 1);
+        if (!tc_cache_of.empty()) tc_cache_of[tc_inst[r]] = (int32_t)(r * VCC_N);
+    }
+    if (tc_fresh && !tc_inst.empty() && !tc_cache_of.empty()) {
+        tc_cache = tc_words;
+        tc_cached = tc_inst;
+    }
+    tc_fresh = false;
     // a kit kind's voice slots: listed by device slot p * npad + kit
     if (pl.m2) {
         const uint32_t W2 = kd->vwords;

@@ -96,10 +96,14 @@ Segments voice_segments(int kind);           // a kit kind's record per voice sl
 // slots [groups][kVevCap] and the overflow list, 8-B records (write_events); with timed events, n_seg >= 2
 // segments: slots [n_seg][groups][kVevCap] | one overflow list | the segments' start frames [n_seg]
 // (olfx_layout.h kSegCap)
+// timed parameters (n_tc >= 1 coefficient records in the launch's segments), after the start frames: the base
+// table [n_seg][groups] (the launch-wide number of a 64-voice group's first record of a segment) | the records,
+// field-major [VCC_N][n_tc], segment by segment and by voice index inside a segment
 struct PacketPlan {
     bool dense;
     size_t o_inst, o_val, o_ev, words;
     size_t n_seg = 1, o_seg = 0;          // o_seg: the start frames (n_seg >= 2)
+    size_t n_tc = 0, o_tcb = 0, o_tc = 0; // timed coefficient records: the base table, the records
     // a kit kind's second section, ahead of the events: the m2 changed voice slots (device slots p * npad + kit,
     // always listed) and their records [W2][m2]
     size_t m2 = 0, o_inst2 = 0, o_val2 = 0;
@@ -107,13 +111,18 @@ struct PacketPlan {
 // n instances of which m changed, W words per record, `evs`: an event section with n_more
 // overflow records for n_ev voice slots (0: the n instances are the voices)
 // n_seg: the event section's segments (timed events)
+// n_tc: the launch's timed coefficient records (olfx_timed_params; 0: no such section)
 PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0, size_t m2 = 0,
-                       uint32_t W2 = 0, uint32_t n_seg = 1);
+                       uint32_t W2 = 0, uint32_t n_seg = 1, size_t n_tc = 0);
 // The largest packet an engine can produce: every instance's coefficients and, for voices, an
 // event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).  A kit
 // kind: every kit's record, every voice slot's record and an event per voice.  n_seg: the segments of a
 // launch (timed events: the voice kinds' kSegCap, max_segments) -- an event for every voice in each.
 size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0, uint32_t n_seg = 1);
+// What the timed-parameter section adds to the largest packet (olfx_timed_params: the voice kinds, else 0): a
+// launch carries at most n coefficient records over all its segments (Shadow::span), so the worst packet grows
+// by one full voice-coefficient upload and the base table, not by kSegCap uploads.
+size_t max_timed_param_words(int kind, uint32_t n);
 // the segments one launch of a kind can take: kSegCap for the kinds olfx_timed_events accepts, else 1
 uint32_t max_segments(int kind);
 // ... for the kinds olfx_timed_notes accepts (the synths and the drum kit): kSegCap, else 1.  An engine's packet
@@ -192,6 +201,26 @@ struct Shadow {
     // the VoiceMap when the engine reaches its frame (fold_segments, advance)
     std::vector<olfx_timed_event> timed;
     std::vector<olfx_voice_event> routed; // fold_segments: one segment's notes as voice events
+    // olfx_timed_params / olfx_timed_control (the voice kinds): the parameter records past frame 0, stably ordered
+    // by frame in one queueing order for both calls; a control is held as the field and value it maps to
+    // (OLFX_FIELD_UPDATE_ONLY: Update() alone).  A record at frame 0 is applied at the call and never listed.
+    std::vector<olfx_timed_param> tparams;
+    // fold_segments: the launch's timed coefficient records -- the voice of each, segment by segment (segment s is
+    // tc_inst[tc_first[s] .. tc_first[s + 1])) and ascending inside a segment, and their words [records][VCC_N].
+    // The voices stay dirty: fill_records puts them back on the list, so their last record reaches the device
+    // arrays ahead of the next launch
+    std::vector<uint32_t> tc_inst, tc_first, tc_words;
+    bool tc_fresh = false;                // fold_segments made them and fill_records has yet to put the voices back
+    // ... and the dirty instances' records as frame 0 has them, derived before the timed records were applied
+    // ([m][words] in fill_records' order; valid for the fold's own fill_records)
+    std::vector<uint32_t> pre_words;
+    bool pre_valid = false;
+    // the last timed record of each voice the previous launch changed: its coefficient words as they stand until
+    // something writes to the voice again (mark_dirty forgets them), so the scatter ahead of the next launch
+    // derives nothing twice.  tc_cache_of[voice] = the record's first word in tc_cache, or -1
+    // tc_cached: the voices that have an entry (a packet without kept records touches none of this)
+    std::vector<int32_t> tc_cache_of;
+    std::vector<uint32_t> tc_cache, tc_cached;
     // fold_events / fold_segments: one record per voice and segment, segment by segment and by first
     // appearance; segment s is folded[seg_first[s] .. seg_first[s + 1]) and starts at frame seg_frame[s]
     std::vector<Folded> folded;
@@ -246,12 +275,20 @@ struct Shadow {
     int voice_events(const olfx_voice_event *ev, uint32_t count);
     int timed_events(const olfx_timed_event *ev, uint32_t count);
     int timed_notes(const olfx_timed_note *ev, uint32_t count);
+    int timed_params(const olfx_timed_param *rec, uint32_t count);
+    int timed_control(const struct olfx_timed_control *rec, uint32_t count);
     // The frames of the next launch of a block of n_frames: all of them, unless more than kSegCap distinct
-    // event times lie in it (frame 0 included, with or without events) -- then up to the first time that
-    // does not fit.
+    // times lie in it (frame 0 included, with or without events; a time is an event's or a timed parameter
+    // record's) -- then up to the first time that does not fit.  Timed parameters bound the launch a second
+    // way: its coefficient records (one per voice changed at a time) number at most n, so the launch ends
+    // before the time whose records would exceed that; one time alone always fits.
     uint32_t span(uint32_t n_frames) const;
     // whether a launch of `span` frames has events
-    bool has_events(uint32_t span_) const { return !events.empty() || (!timed.empty() && timed.front().frame < span_); }
+    bool has_events(uint32_t span_) const {
+        return !events.empty() || (!timed.empty() && timed.front().frame < span_) || has_timed_params(span_);
+    }
+    // ... has timed parameter records (they are past frame 0: the launch is segmented)
+    bool has_timed_params(uint32_t span_) const { return !tparams.empty() && tparams.front().frame < span_; }
     // After a launch of `span` frames: the pending events' frames count from the next launch (an event at
     // frame `span` is at its frame 0).  fold_segments(span) has taken the events below `span`.  An instrument
     // note that reaches frame 0 is routed here, ahead of anything queued from now on.
@@ -287,7 +324,7 @@ struct Shadow {
     uint32_t n_chunks(uint32_t span_, uint32_t chunk) const;
     PacketPlan plan(bool evs) const {
         return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords,
-                           evs ? n_seg() : 1u);
+                           evs ? n_seg() : 1u, evs ? tc_inst.size() : 0u);
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
@@ -297,6 +334,8 @@ struct Shadow {
     bool ring_free_next() const;
     // The folded records into the event section `fix` (buf + o_ev).
     void write_events(uint32_t *fix);
+    // The timed coefficient section (pl.n_tc >= 1): the base table and the records into `buf`.
+    void write_timed_coefs(const PacketPlan &pl, uint32_t *buf) const;
 
 private:
     int fail(int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -318,8 +357,13 @@ private:
     }
     // the pending list whose entries from `old` on are new: stably by frame, behind the queued ones of their frame
     void merge_timed(size_t old);
-    // one segment's events onto `folded`, ev_count and ev_more
-    void fold_one(const olfx_voice_event *ev, size_t count, size_t stride);
+    // one segment's events onto `folded`, ev_count and ev_more; `coef`: the voices whose coefficients change at the
+    // segment's start (VEV_COEF, alone or with the voice's events)
+    void fold_one(const olfx_voice_event *ev, size_t count, size_t stride, const uint32_t *coef = nullptr, size_t n_coef = 0);
+    // one validated parameter record on params / configured, as olfx_set_param (or, OLFX_FIELD_UPDATE_ONLY,
+    // Update()) of that voice; `mark`: onto the dirty list as well
+    void apply_param(const olfx_timed_param &r, bool mark);
+    int queue_params(const olfx_timed_param *rec, size_t count);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
         return kd->instances == KindDesc::VOICES || (n_fields && field0 < kd->voice_end && field0 + n_fields > kd->voice0);

@@ -238,6 +238,13 @@ struct VoiceArgs {
     // n_seg <= 1: one segment, the launch as it was
     uint32_t n_seg, n_chunks;
     const uint32_t *seg;
+    // timed parameters (the segmented kernels; nullptr: none): tc_n coefficient records, field-major [VCC_N][tc_n],
+    // segment by segment and by voice inside a segment; tc_base[s n_groups + g] = the number of group g's first
+    // record of segment s.  A voice has a record in a segment iff its event record there has VEV_COEF; it is
+    // record tc_base + (the group's lower voices with VEV_COEF in that segment)
+    const uint32_t *tc_base;
+    const uint32_t *tc;
+    uint32_t tc_n;
 };
 
 // Coefficient records of the instances whose parameters changed (olfx_engine.cpp submit_control):

@@ -131,6 +131,9 @@ enum : uint32_t {
     VEV_RETRIGGER = 4u,         // Adsr::Retrigger(true) on both envelopes: mode ATTACK, x = 0
     VEV_FREQ = 8u,              // freq_ := the record's frequency (mtof(note) for NoteOn, SetFrequency's Hz)
     VEV_SEEK = 0x10u,           // sample voices: Seek(0) (SampleSoundSource::GateOn, any NoteOn / GateOn of the block)
+    // timed parameters (segments past the first): the voice's coefficients change at the segment's start; its
+    // record is in the packet's timed coefficient section (VoiceArgs::tc).  May be a record's only bit
+    VEV_COEF = 0x20u,
     VEV_MORE = 0x80u,           // (slot 0 of a crowded workgroup) its records are in the overflow list
 };
 // Event records, 8 B: x = (voice & 63) | VEV_* ops << 8, y = frequency bits; x = 0 is an empty slot.

@@ -76,14 +76,15 @@ __device__ __forceinline__ void voice_v4(const VoiceArgs &a) {
             apply_gate_events(ev, flags0, xa0, xf0);
         }
         bool gate = (flags0 >> 8) & 1u;
-        const float amp_amt = c[VCC_AMP_AMT * n + i], port_c = c[VCC_PORT_COEF * n + i];
+        // (SEG: the coefficients are loop-carried -- a segment with VEV_COEF replaces them)
+        float amp_amt = c[VCC_AMP_AMT * n + i], port_c = c[VCC_PORT_COEF * n + i];
         const float inv_sr = c[VCC_INV_SR * n + i];
         float freq = (ev.op & VEV_FREQ) ? ev.freq : freq_s;
         [[maybe_unused]] bool fset = false;               // SEG: some segment set the frequency
-        const float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
+        float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
         // ladder: drive_scaled (VCC_DRIVE), 1/(4 sr) (VCC_FC_MAX)
-        const float drive = c[VCC_DRIVE * n + i];
-        const float fc_max = c[VCC_FC_MAX * n + i];
+        float drive = c[VCC_DRIVE * n + i];
+        float fc_max = c[VCC_FC_MAX * n + i];
         float phase = s[VCS_PHASE * n + i];
         float port_z = s[VCS_PORT_Z * n + i];
         bool gprev_a = (flags0 >> 6) & 1u, gprev_f = (flags0 >> 7) & 1u;
@@ -116,6 +117,19 @@ __device__ __forceinline__ void voice_v4(const VoiceArgs &a) {
                             xf0 = ef.x;
                         }
                         const VoiceEv sev = seg_event(*sg, cu.seg, me);
+                        if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, sev, n, me); r != kNoCoef) {
+                            // timed parameters: the segment's coefficients first, then what a launch's start does
+                            ca[0] = seg_coef(a, r, VCC_ATK_D0A); ca[1] = seg_coef(a, r, VCC_ATK_TGT_A); ca[2] = seg_coef(a, r, VCC_DEC_D0A);
+                            ca[3] = seg_coef(a, r, VCC_REL_D0A); ca[4] = seg_coef(a, r, VCC_SUS_A);
+                            cf[0] = seg_coef(a, r, VCC_ATK_D0F); cf[1] = seg_coef(a, r, VCC_ATK_TGT_F); cf[2] = seg_coef(a, r, VCC_DEC_D0F);
+                            cf[3] = seg_coef(a, r, VCC_REL_D0F); cf[4] = seg_coef(a, r, VCC_SUS_F);
+                            amp_amt = seg_coef(a, r, VCC_AMP_AMT);
+                            cutoff = seg_coef(a, r, VCC_CUTOFF);
+                            fenv_amt = seg_coef(a, r, VCC_FENV_AMT);
+                            fc_max = seg_coef(a, r, VCC_FC_MAX);
+                            port_c = seg_coef(a, r, VCC_PORT_COEF);
+                            drive = seg_coef(a, r, VCC_LADDER_DRIVE);
+                        }
                         apply_gate_events(sev, flags0, xa0, xf0);
                         gate = (flags0 >> 8) & 1u;
                         gprev_a = (flags0 >> 6) & 1u;
@@ -164,7 +178,7 @@ __device__ __forceinline__ void voice_v4(const VoiceArgs &a) {
         feed(std::true_type{}, std::true_type{});
     } else {
         // ---------------- filter role: LadderFilter::Process ----------------
-        const float k_or_unused = c[VCC_DAMP_RES * n + i];     // ladder: K (VCC_LADDER_K)
+        float k_or_unused = c[VCC_DAMP_RES * n + i];           // ladder: K (VCC_LADDER_K); SEG: loop-carried
         Ladder L;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -176,6 +190,11 @@ __device__ __forceinline__ void voice_v4(const VoiceArgs &a) {
         SegCursor<SEG> cu(sg, a.n_seg);
         for (uint32_t k = 0; k <= nchunks; ++k) {
             if (k > 0) {
+                if constexpr (SEG) {
+                    if (cu.first && a.tc)        // timed parameters: this segment's resonance
+                        if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, seg_event(*sg, cu.seg, me), n, me); r != kNoCoef)
+                            k_or_unused = seg_coef(a, r, VCC_LADDER_K);
+                }
                 const uint32_t f0 = SEG ? (uint32_t)cu.f0 : (k - 1) * kVcChunk;
                 const uint32_t m = SEG ? cu.len() : (nf - f0 < (uint32_t)kVcChunk ? nf - f0 : (uint32_t)kVcChunk);
                 const float4 *qb = &q[(k - 1) & 1][0][lane];
@@ -248,7 +267,7 @@ __device__ __forceinline__ void voice_v5(const VoiceArgs &a) {
     } else if (role == 1) {
         // ---- OSC (SynthVoice.h:44-45): Port::Process, Oscillator::SetFreq / Process, WAVE_POLYBLEP_SAW,
         //      amp 0.5 ----
-        const float port_c = c[VCC_PORT_COEF * n + i];
+        float port_c = c[VCC_PORT_COEF * n + i];          // (SEG: a segment with VEV_COEF replaces it)
         const float inv_sr = c[VCC_INV_SR * n + i];
         float freq = s[VCS_FREQ * n + i];
         float phase = s[VCS_PHASE * n + i], port_z = s[VCS_PORT_Z * n + i];
@@ -268,6 +287,8 @@ __device__ __forceinline__ void voice_v5(const VoiceArgs &a) {
                 if constexpr (SEG) {
                     if (cu.first) {              // the segment's pitch events, staged by ENV before the first barrier
                         const VoiceEv ev = seg_event(*sg, cu.seg, me);
+                        if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, ev, n, me); r != kNoCoef)
+                            port_c = seg_coef(a, r, VCC_PORT_COEF);       // timed parameters: this segment's portamento
                         if (ev.op & VEV_FREQ) {
                             freq = ev.freq;
                             fset = true;

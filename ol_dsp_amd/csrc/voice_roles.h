@@ -95,8 +95,10 @@ __device__ __forceinline__ VoiceEv staged_event(const VoiceArgs &a, const uint2 
 // records, slot = voice within the group.  A slot set per segment, all staged before the first barrier:
 // a role that runs a step or two behind ENV reads a segment's records however short the segments are,
 // and the host-link reads of all segments are in flight together, ahead of the chunk loop.
+// ... and, with timed parameters, the number of the group's first coefficient record of each segment (tc_base).
 struct VoiceSegs {
     uint32_t start[kSegCap + 1];
+    uint32_t cbase[kSegCap];
     uint2 slot[kSegCap][64];
 };
 // The bounds, by the workgroup's first threads (the caller's next barrier publishes them); clamped to the
@@ -107,6 +109,7 @@ __device__ __forceinline__ void voice_segs_bounds(const VoiceArgs &a, VoiceSegs 
         const uint32_t f = (t == 0u || t == S) ? 0u : a.seg[t];
         sg.start[t] = t == S ? a.n_frames : (f < a.n_frames ? f : a.n_frames);
     }
+    if (t < S && t < kSegCap) sg.cbase[t] = a.tc_base ? a.tc_base[(size_t)t * ((a.n + 63u) / 64u) + blockIdx.x] : 0u;
 }
 // Every segment's records of `group` into sg.slot, by one wave: all the fixed-slot reads first (one
 // host-link round trip for the lot), then the crowded segments' overflow runs (a second), then the slots.
@@ -146,6 +149,28 @@ __device__ __forceinline__ VoiceEv seg_event(const VoiceSegs &sg, uint32_t seg, 
     const uint2 v = sg.slot[seg][me];
     return VoiceEv{v.x, __uint_as_float(v.y)};
 }
+// Timed parameters (olfx_timed_params): a voice whose segment record has VEV_COEF takes new coefficients at that
+// segment's start.  Each role reloads its own words at ITS segment start (the roles run a step or two apart),
+// before it does what it does at a launch's start, and keeps them until the voice's next such record.  The
+// records are read straight from the packet; no per-record index: a group's records of a segment are
+// consecutive from cbase[seg], by voice, so a lane's is cbase + the lower live lanes that have one too.  Dead
+// lanes of the last group mirror voice n - 1: they are left out of the vote and take that lane's rank (`me`).
+// Returns the record's number, or kNoCoef (also for a number outside the section, whatever the packet holds).
+constexpr uint32_t kNoCoef = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t seg_coef_record(const VoiceArgs &a, const VoiceSegs &sg, uint32_t seg, const VoiceEv &ev,
+                                                    uint32_t n, uint32_t me) {
+    if (!a.tc) return kNoCoef;                             // a launch without timed parameters: one scalar test
+    const bool has = (ev.op & VEV_COEF) != 0u;
+    const bool live = blockIdx.x * 64u + (threadIdx.x & 63u) < n;
+    const uint64_t votes = __builtin_amdgcn_ballot_w64(has && live);
+    if (!votes) return kNoCoef;                            // wave-uniform: the common segment start
+    const uint32_t r = sg.cbase[seg] + (uint32_t)__builtin_popcountll(votes & ((1ull << me) - 1ull));
+    return has && r < a.tc_n ? r : kNoCoef;
+}
+__device__ __forceinline__ float seg_coef(const VoiceArgs &a, uint32_t r, uint32_t word) {
+    return __uint_as_float(a.tc[(size_t)word * a.tc_n + r]);
+}
+
 // A role's place in the launch's chunk sequence (wave-uniform): the chunk's first frame, its segment and
 // whether it starts it.  SEG = false: nothing (the roles index chunks by step, as they always have).
 template <bool SEG>
@@ -401,9 +426,10 @@ __device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLa
     }
     bool gate = (flags0 >> 8) & 1u;
     bool gprev_a = (flags0 >> 6) & 1u, gprev_f = (flags0 >> 7) & 1u;
-    const float amp_amt = c[VCC_AMP_AMT * n + i], fc_max = c[VCC_FC_MAX * n + i];
-    const float amp_half = 0.5f * amp_amt;       // FILT's Low() halving folded in (exact scaling)
-    const float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
+    // (SEG: loop-carried -- a segment with VEV_COEF replaces them)
+    float amp_amt = c[VCC_AMP_AMT * n + i], fc_max = c[VCC_FC_MAX * n + i];
+    float amp_half = 0.5f * amp_amt;             // FILT's Low() halving folded in (exact scaling)
+    float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
     Env ea, ef;
     // (SEG: the envelope coefficients stay in registers for the segment starts)
     [[maybe_unused]] float ca[5], cf[5];
@@ -428,7 +454,20 @@ __device__ __forceinline__ void voice_role_env(const VoiceArgs &a, const VoiceLa
                         xa0 = ea.x;
                         xf0 = ef.x;
                     }
-                    apply_gate_events(seg_event(*sg, cu.seg, me), flags0, xa0, xf0);
+                    const VoiceEv sev = seg_event(*sg, cu.seg, me);
+                    if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, sev, n, me); r != kNoCoef) {
+                        // timed parameters: the segment's coefficients first, then what a launch's start does
+                        ca[0] = seg_coef(a, r, VCC_ATK_D0A); ca[1] = seg_coef(a, r, VCC_ATK_TGT_A); ca[2] = seg_coef(a, r, VCC_DEC_D0A);
+                        ca[3] = seg_coef(a, r, VCC_REL_D0A); ca[4] = seg_coef(a, r, VCC_SUS_A);
+                        cf[0] = seg_coef(a, r, VCC_ATK_D0F); cf[1] = seg_coef(a, r, VCC_ATK_TGT_F); cf[2] = seg_coef(a, r, VCC_DEC_D0F);
+                        cf[3] = seg_coef(a, r, VCC_REL_D0F); cf[4] = seg_coef(a, r, VCC_SUS_F);
+                        amp_amt = seg_coef(a, r, VCC_AMP_AMT);
+                        cutoff = seg_coef(a, r, VCC_CUTOFF);
+                        fenv_amt = seg_coef(a, r, VCC_FENV_AMT);
+                        fc_max = seg_coef(a, r, VCC_FC_MAX);
+                        amp_half = 0.5f * amp_amt;
+                    }
+                    apply_gate_events(sev, flags0, xa0, xf0);
                     gate = (flags0 >> 8) & 1u;
                     gprev_a = (flags0 >> 6) & 1u;
                     gprev_f = (flags0 >> 7) & 1u;
@@ -493,11 +532,16 @@ __device__ __forceinline__ void voice_role_freq(const VoiceArgs &a, const VoiceL
                                                 const VoiceSegs *sg = nullptr) {
     const uint32_t n = v.n, lane = v.lane, i = v.i, nsteps = v.nsteps;
     const float *c = a.coef;
-    const float damp_res = c[VCC_DAMP_RES * n + i];
+    float damp_res = c[VCC_DAMP_RES * n + i];    // (SEG: a segment with VEV_COEF replaces it)
     const float inv_2sr = 1.0f / (c[VCC_SR * n + i] * 2.0f);
     SegCursor<SEG> cu(sg, a.n_seg);
     for (uint32_t k = 0; k < nsteps; ++k) {
         if (k >= 1 && k + 1 < nsteps) {
+            if constexpr (SEG) {
+                if (cu.first && a.tc)            // timed parameters: this segment's damping
+                    if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, seg_event(*sg, cu.seg, v.me), n, v.me); r != kNoCoef)
+                        damp_res = seg_coef(a, r, VCC_DAMP_RES);
+            }
             const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k - 1); }();
             const float2 *qi = &eq[(k - 1) % 3][0][lane];
             float2 *qo = &fdq[(k - 1) & 1][0][lane];
@@ -561,11 +605,16 @@ __device__ __forceinline__ void voice_role_filt(const VoiceArgs &a, const VoiceL
     const uint32_t n = v.n, lane = v.lane, i = v.i, nsteps = v.nsteps;
     const float *c = a.coef;
     float *s = a.state;
-    const float drive = c[VCC_DRIVE * n + i];
+    float drive = c[VCC_DRIVE * n + i];          // (SEG: a segment with VEV_COEF replaces it)
     float low = s[VCS_LOW * n + i], band = s[VCS_BAND * n + i];
     SegCursor<SEG> cu(sg, a.n_seg);
     for (uint32_t k = 0; k < nsteps; ++k) {
         if (k >= 2) {
+            if constexpr (SEG) {
+                if (cu.first && a.tc)            // timed parameters: this segment's drive
+                    if (const uint32_t r = seg_coef_record(a, *sg, cu.seg, seg_event(*sg, cu.seg, v.me), n, v.me); r != kNoCoef)
+                        drive = seg_coef(a, r, VCC_DRIVE);
+            }
             const uint32_t f0 = SEG ? (uint32_t)cu.f0 : (k - 2) * kVcChunk;
             const uint32_t m = [&] { if constexpr (SEG) return cu.len(); else return v.len(k - 2); }();
             // the chunk's output rows through a buffer resource based at row f0: the row offset

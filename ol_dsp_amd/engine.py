@@ -287,6 +287,75 @@ class Engine:
             arr[k].ev.velocity = 100
         check(self.lib.olfx_timed_notes(self._h, arr, len(evs)), self._h)
 
+    def make_timed_params(self, frames, inst, field, values):
+        """A prebuilt record array (numpy-vectorised) for timed_params: frame / inst / value arrays (or scalars
+        broadcast against inst) of one field (name or index)."""
+        inst = np.asarray(inst, np.uint32).ravel()
+        rec = np.zeros(len(inst), dtype=[("frame", "<u4"), ("inst", "<u4"), ("field", "<u4"), ("value", "<f4")])
+        rec["frame"] = frames
+        rec["inst"] = inst
+        rec["field"] = self.field(field)
+        rec["value"] = values
+        assert ctypes.sizeof(_lib.TimedParam) == rec.dtype.itemsize
+        return rec
+
+    def timed_params(self, records) -> None:
+        """Parameter changes at a frame inside the coming blocks (the voice kinds; olfx_timed_params): iterable of
+        (frame, inst, field, value), or an array from make_timed_params().  Each is set_param at its frame: frame
+        counts from the first frame of the next process() and is a multiple of 4; at a frame, parameter changes
+        precede the events; a record past the block stays pending."""
+        if isinstance(records, np.ndarray):
+            if len(records):
+                check(self.lib.olfx_timed_params(self._h, records.ctypes.data_as(ctypes.POINTER(_lib.TimedParam)),
+                                                 len(records)), self._h)
+            return
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.TimedParam * len(recs))()
+        for k, r in enumerate(recs):
+            arr[k].frame = int(r[0])
+            arr[k].inst = int(r[1])
+            arr[k].field = self.field(r[2])
+            arr[k].value = float(r[3])
+        check(self.lib.olfx_timed_params(self._h, arr, len(recs)), self._h)
+
+    @staticmethod
+    def make_timed_control(frames, inst, cc, values, source="midi"):
+        """A prebuilt record array (numpy-vectorised) for timed_control: frame / inst / cc / value arrays (or
+        scalars broadcast against inst); source "midi" (value 0..127) or "hw"."""
+        inst = np.asarray(inst, np.uint32).ravel()
+        rec = np.zeros(len(inst), dtype=[("frame", "<u4"), ("inst", "<u4"), ("control", "u1"), ("source", "u1"),
+                                         ("pad", "<u2"), ("value", "<f4")])
+        rec["frame"] = frames
+        rec["inst"] = inst
+        rec["control"] = cc
+        rec["source"] = _lib.CTL_HARDWARE if source in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
+        rec["value"] = values
+        assert ctypes.sizeof(_lib.TimedControl) == rec.dtype.itemsize
+        return rec
+
+    def timed_control(self, records) -> None:
+        """Control changes at a frame inside the coming blocks (the voice kinds; olfx_timed_control): iterable of
+        (frame, inst, cc, value[, source]), or an array from make_timed_control().  Each is control() at its
+        frame; controls the reference ignores are skipped."""
+        if isinstance(records, np.ndarray):
+            if len(records):
+                check(self.lib.olfx_timed_control(self._h, records.ctypes.data_as(ctypes.POINTER(_lib.TimedControl)),
+                                                  len(records)), self._h)
+            return
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.TimedControl * len(recs))()
+        for k, r in enumerate(recs):
+            arr[k].frame = int(r[0])
+            arr[k].ev.inst = int(r[1])
+            arr[k].ev.control = int(r[2])
+            arr[k].ev.value = float(r[3])
+            arr[k].ev.source = _lib.CTL_HARDWARE if len(r) > 4 and r[4] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
+        check(self.lib.olfx_timed_control(self._h, arr, len(recs)), self._h)
+
     def update(self, first: int = 0, count: int = -1) -> None:
         """Update() of instances first..first+count with their current parameters."""
         count = self.n - first if count < 0 else count
