@@ -596,6 +596,40 @@ struct olfx_timed_control {
 };
 int olfx_timed_params(olfx_engine *e, const olfx_timed_param *rec, uint32_t n);
 int olfx_timed_control(olfx_engine *e, const struct olfx_timed_control *rec, uint32_t n);
+/* The same for OLFX_KIND_SYNTH, OLFX_KIND_SYNTH_SVF and OLFX_KIND_DRUMKIT, with the same record types: `inst` is the
+   instrument or kit, `field` an OLFX_SY_* / OLFX_DK_* index, and for a kit ev.pad the MIDI channel or
+   OLFX_DK_CHANNEL_RACK.  So a MIDI buffer of notes (olfx_timed_notes) and CCs can be queued whole.  One
+   olfx_process(N) computes, bit for bit in output and stored state, what one olfx_process per distinct time below N
+   computes -- a time being the frame of a timed note or of one of these records -- when before each call that
+   time's records are applied by olfx_set_param / olfx_control in queueing order (both calls share one order) and
+   that time's notes are then handed to olfx_note_events; olfx_synth_playing and olfx_get_param read the same after
+   both.  At a frame, parameter changes precede notes whatever the queueing order: the block-boundary rule.
+     - a record at frame 0 is exactly olfx_set_param / olfx_control now;
+     - a record at or past N stays pending with its frame reduced by N; one whose frame becomes 0 is applied as
+       that olfx_process returns, ahead of anything set afterwards; olfx_reset drops pending records;
+     - a control is mapped when the engine reaches its frame, not here (unlike the voice kinds'): under the
+       instrument's topology at that frame -- a TOPOLOGY record at frame 8 changes what CC 45 at frame 12 maps to
+       -- and, for a kit, the channel2voice table in force at that olfx_process, as timed notes use the map;
+     - the fan-out is olfx_control's: on the synths the voices, then the rack (CCs 41-44 hit the voice filter and
+       FILTER_* at topology 1); on a kit the channel's voice alone, or the rack.  OLFX_FIELD_UPDATE_ONLY is Update()
+       of the voices it reaches, at that frame; a control the reference ignores is skipped;
+     - a write to a voice field is UpdateConfig + Update() of every voice of the instrument on the synths and
+       Update() of exactly that voice slot on a kit, as olfx_set_param; fields of slots p >= P are stored only;
+     - olfx_set_params, olfx_set_param_list, olfx_control, olfx_update, olfx_drumkit_map, olfx_sample_voices and
+       olfx_sample_bank keep landing at the block boundary, ahead of every pending record.
+   Cost.  Record times and note times share the 16 segments of a launch.  The voice fields and REVERB_BALANCE,
+   FILTER_CUTOFF, FILTER_RESONANCE, FILTER_DRIVE, FILTER_TYPE and MASTER_VOLUME change at their frame inside one
+   launch.  DELAY_TIME, DELAY_FEEDBACK, DELAY_BALANCE, DELAY_CUTOFF, DELAY_RESONANCE and TOPOLOGY obey the same
+   contract, but the delay stage's geometry is fixed per launch: a call with such a change -- or with CC 35-39 to a
+   rack, which may map to one -- runs as several launches, one ending at each such time.  A launch also takes at
+   most n_inst raw records (a kit: voices x n_inst; a time's records count as that many at the most, so one time
+   always fits); a call with more runs as several launches.
+   OLFX_E_ARG (nothing is queued, the shadow is untouched): null with n > 0, a frame that is no multiple of 4 or
+   not below 2^31, inst or field out of range, a value olfx_set_param refuses (a topology the kind does not accept
+   among them), a control record olfx_control refuses on that kind under any topology the kind accepts.
+   OLFX_E_KIND: the three voice kinds (olfx_timed_params).  OLFX_E_STATE: effect and meter kinds. */
+int olfx_timed_instrument_params(olfx_engine *e, const olfx_timed_param *rec, uint32_t n);
+int olfx_timed_instrument_control(olfx_engine *e, const struct olfx_timed_control *rec, uint32_t n);
 /* OLFX_KIND_SYNTH / OLFX_KIND_SYNTH_SVF / OLFX_KIND_DRUMKIT: Playing() of the `voices` voices of instrument (kit) inst,
    as of the calls made so far (with timed notes: as of the frames processed so far). */
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing /*[voices]*/);

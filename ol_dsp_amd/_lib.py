@@ -202,6 +202,8 @@ SIGNATURES = {
     "olfx_timed_notes": (ctypes.c_int, [_P, ctypes.POINTER(TimedNote), _U32]),
     "olfx_timed_params": (ctypes.c_int, [_P, ctypes.POINTER(TimedParam), _U32]),
     "olfx_timed_control": (ctypes.c_int, [_P, ctypes.POINTER(TimedControl), _U32]),
+    "olfx_timed_instrument_params": (ctypes.c_int, [_P, ctypes.POINTER(TimedParam), _U32]),
+    "olfx_timed_instrument_control": (ctypes.c_int, [_P, ctypes.POINTER(TimedControl), _U32]),
     "olfx_update": (ctypes.c_int, [_P, _U32, _U32]),
     "olfx_control_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint8, ctypes.c_int, _F, ctypes.POINTER(_U32),
                                         ctypes.POINTER(_F)]),

@@ -64,6 +64,7 @@ struct DkVoice : VoiceEnvs {
     float low, band;
     SvfVoiceCoef kc;
     uint32_t base, len, ls, le, limit, pos, mg;
+    uint32_t crec;                                         // SEG: the slot's latest timed voice record, or kNoCoef
     bool loop, playing;
 };
 }  // namespace
@@ -71,8 +72,13 @@ struct DkVoice : VoiceEnvs {
 // SEG (drumkit_block_v1_seg; olfx_timed_notes): the launch's frames are a.n_seg segments with note events of their
 // own; the V waves split their chunks at the segment starts (sy::role_v) and fetch per piece, so a cooperative load
 // never spans a Seek -- its latency is exposed once per segment start.  D and F are the same code.
-template <bool SEG>
-__global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
+// TP (drumkit_block_v1_seg_tp; a.tp; olfx_timed_instrument_params; a SEG launch whose packet has timed records -- one
+// without runs the SEG kernel as it was): a voice slot with a voice record at a segment
+// start takes its coefficients (v.kc) from it ahead of the segment's events and remembers the record, whose
+// envelope words voice_envs_restart reads from then on.  F takes the kit's rack records (sy::role_f).
+template <bool SEG, bool TP = false>
+__global__ __launch_bounds__(sy::kThreads) void drumkit_block(std::conditional_t<TP, DrumkitSegArgs, DrumkitArgs> a) {
+    static_assert(SEG || !TP, "timed records come with segments");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const sy::Wg b = sy::enter(a, lds);
     const uint32_t P = b.P;
@@ -96,6 +102,7 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
                                                i - b.g * 64u, p * (a.npad >> 6) + b.g);
             v.low = s[VCS_LOW * sn + si];
             v.band = s[VCS_BAND * sn + si];
+            v.crec = kNoCoef;
             // the slot's own coefficients, as voice_role_env / voice_role_freq form them (Port and Oscillator unused)
             v.kc = SvfVoiceCoef{0.5f * c[VCC_AMP_AMT * sn + si], 0.0f, 0.0f, c[VCC_CUTOFF * sn + si],
                                 c[VCC_FENV_AMT * sn + si], c[VCC_FC_MAX * sn + si], c[VCC_DRIVE * sn + si],
@@ -200,7 +207,7 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
                     if (k < m) q[k * 64u] = svf_voice_tick_src(v.ea, v.ef, v.low, v.band, x[k], v.kc);
             }
         };
-        if constexpr (SEG) {
+        if constexpr (SEG && !TP) {
             // a segment's events on the live voice, as load applies the block's: the gate and the envelopes, Seek(0),
             // Play() / Pause(), and the stored pitch (the last segment's value wins)
             auto start = [&](DkVoice &v, uint32_t p, const VoiceEv &ev) {
@@ -211,6 +218,25 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
                 if (ev.op & VEV_FREQ) s[VCS_FREQ * sn + si] = ev.freq;
             };
             sy::role_v<DkVoice, float[sy::kChunk], true>(b, load, run, store, fetch, &a, start);
+        } else if constexpr (TP) {
+            // ... and ahead of them the slot's voice record of the segment, if it has one
+            auto start = [&](DkVoice &v, uint32_t p, const VoiceEv &ev, uint32_t r) {
+                const uint32_t si = p * a.npad + i;
+                const float *t = a.tp.vrec;
+                const uint32_t T = a.tp.n_v;
+                if (r != kNoCoef) {
+                    v.crec = r;
+                    v.kc = SvfVoiceCoef{0.5f * t[VCC_AMP_AMT * T + r], 0.0f, 0.0f, t[VCC_CUTOFF * T + r],
+                                        t[VCC_FENV_AMT * T + r], t[VCC_FC_MAX * T + r], t[VCC_DRIVE * T + r],
+                                        t[VCC_DAMP_RES * T + r], 1.0f / (t[VCC_SR * T + r] * 2.0f)};
+                }
+                const bool rec = v.crec != kNoCoef;
+                voice_envs_restart(v, ev, rec ? t : c, rec ? T : sn, rec ? v.crec : si);
+                if (ev.op & VEV_SEEK) v.pos = 0u;
+                if (ev.op & VEV_GATE_SET) v.playing = (ev.op & VEV_GATE_ON) != 0u;
+                if (ev.op & VEV_FREQ) s[VCS_FREQ * sn + si] = ev.freq;
+            };
+            sy::role_v<DkVoice, float[sy::kChunk], true, true>(b, load, run, store, fetch, &a, start, &a.tp);
         } else {
             sy::role_v<DkVoice, float[sy::kChunk]>(b, load, run, store, fetch);
         }
@@ -230,14 +256,20 @@ __global__ __launch_bounds__(sy::kThreads) void drumkit_block(DrumkitArgs a) {
             }
         });
     } else {
-        sy::role_f<true>(b, a);
+        sy::role_f<true, TP>(b, a, [&]() -> const InstrumentTimed * {
+            if constexpr (TP) return &a.tp;
+            else return nullptr;
+        }());
     }
 }
 
-hipError_t launch_drumkit(const DrumkitArgs &a, hipStream_t s) {
+hipError_t launch_drumkit(const DrumkitSegArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
-    if (!instrument_args_ok(a, kDkMaxVoices) || (a.bank_bytes && !a.bank)) return hipErrorInvalidValue;
-    return sy::launch(a.n_seg > 1u ? drumkit_block<true> : drumkit_block<false>, a, kDkTile, s);
+    if (!instrument_args_ok(a, kDkMaxVoices) || (a.bank_bytes && !a.bank) || !instrument_timed_ok(a, a.tp, true))
+        return hipErrorInvalidValue;
+    if (a.tp.vtab) return sy::launch(drumkit_block<true, true>, a, kDkTile, s);
+    const DrumkitArgs &plain = a;                          // (the other kernels take the arguments they always took)
+    return sy::launch(a.n_seg > 1u ? drumkit_block<true> : drumkit_block<false>, plain, kDkTile, s);
 }
 
 }  // namespace olfx

@@ -350,7 +350,9 @@ ChorusArgs chorus_args(const olfx_engine *e, uint32_t n_frames, uint64_t plane) 
 // itself.  A slot is rewritten only after the kernels that read it are done (its `consumed` event,
 // recorded by the caller after them: *used_slot).
 // `span`: the frames of the launch the packet is for (timed events below it become its segments).
-int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Slot **used_slot, uint32_t span) {
+// `tp`: the packet's timed instrument section for the launch (the synths and the drum kit), if it has one.
+int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, InstrumentTimed *tp, olfx_engine::Slot **used_slot,
+                   uint32_t span) {
     *used_slot = nullptr;
     host::Shadow &hs = e->hs;
     const bool evs = host::takes_note_events(e->kind) && hs.has_events(span);
@@ -402,6 +404,7 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
     lap(3);
     if (evs) hs.write_events(sl.h + pl.o_ev);
     if (pl.n_tc) hs.write_timed_coefs(pl, sl.h);
+    if (pl.n_iv + pl.n_if) hs.write_timed_inst(pl, sl.h);
     if (copy) {
         // the copy stream waits for nothing on the device: the host made sure above that the slot's
         // previous readers are done (a device-side wait there serialised the copy behind them)
@@ -443,6 +446,15 @@ int submit_control(olfx_engine *e, hipStream_t s, VoiceArgs *va, olfx_engine::Sl
                 va->tc_base = dev + pl.o_tcb;
                 va->tc = dev + pl.o_tc;
                 va->tc_n = (uint32_t)pl.n_tc;
+            }
+            if (pl.n_iv + pl.n_if) {      // timed instrument parameters: the segments' voice and rack records
+                tp->vtab = reinterpret_cast<const uint4 *>(dev + pl.o_ivt);
+                tp->ftab = reinterpret_cast<const uint4 *>(dev + pl.o_ift);
+                tp->vrec = reinterpret_cast<const float *>(dev + pl.o_iv);
+                tp->frec = dev + pl.o_if;
+                tp->n_v = (uint32_t)pl.n_iv;
+                tp->n_f = (uint32_t)pl.n_if;
+                tp->gv = (uint32_t)pl.gv;
             }
         }
     }
@@ -521,7 +533,7 @@ int ensure_staging(olfx_engine *e, size_t fin, size_t fout) {
 // One launch over frames [e->frames, e->frames + n_frames) of every instance: in / out hold those
 // frames with channel planes `plane` floats apart.  `ev` carries the block's note events (voices).
 int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uint64_t plane, hipStream_t s,
-           const VoiceArgs &ev) {
+           const VoiceArgs &ev, const InstrumentTimed &tp) {
     hipError_t r = hipSuccess;
     const uint32_t t0 = (uint32_t)(e->frames & 0xFFFFFFFFu);
     auto dt_args = [&](const float *in, float *out) {
@@ -669,16 +681,18 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
     case OLFX_KIND_SYNTH:
     case OLFX_KIND_SYNTH_SVF: {
         // one fused launch: the voice waves feed the delay waves and the filter wave through LDS
-        SynthArgs a{};
+        SynthSegArgs a{};
         instrument_args(a);
         a.svf = e->kind == OLFX_KIND_SYNTH_SVF;
+        a.tp = tp;
         r = launch_synth(a, s);
         break;
     }
     case OLFX_KIND_DRUMKIT: {
         // one fused launch: the sample-voice waves feed the delay waves and the filter wave through LDS
-        DrumkitArgs a{};
+        DrumkitSegArgs a{};
         instrument_args(a);
+        a.tp = tp;
         a.smp = e->sm_asg;
         a.order = e->dk_order;
         a.bank = e->sm_bank;
@@ -732,12 +746,13 @@ int launch(olfx_engine *e, const float *din, float *dout, uint32_t n_frames, uin
 // more times than a launch takes: in / out point at the run's first frame, and the channel planes keep the
 // call's distance).
 int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, uint32_t call_frames, hipStream_t s,
-               const VoiceArgs &ev) {
+               const VoiceArgs &ev, const InstrumentTimed &tp) {
     const uint64_t n = e->n, plane = (uint64_t)call_frames * n;
     const uint64_t lim = (1ull << 30) - 1;                     // floats addressable in 32-bit bytes
     const VoiceArgs none{};
+    const InstrumentTimed no_tp{};
     if (!e->hs.kd->planes_32bit || plane + plane <= lim) {
-        const int rc = launch(e, in, out, n_frames, plane, s, ev);
+        const int rc = launch(e, in, out, n_frames, plane, s, ev, tp);
         if (rc) return rc;
         e->frames += n_frames;
         return OLFX_OK;
@@ -747,7 +762,7 @@ int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, u
         for (uint32_t f0 = 0; f0 < n_frames; f0 += F) {
             const uint32_t Ft = std::min(F, n_frames - f0);
             const int rc = launch(e, in ? in + (size_t)f0 * n : nullptr, out + (size_t)f0 * n, Ft, plane, s,
-                                  f0 ? none : ev);
+                                  f0 ? none : ev, f0 ? no_tp : tp);
             if (rc) return rc;
             e->frames += Ft;
         }
@@ -771,7 +786,7 @@ int run_frames(olfx_engine *e, const float *in, float *out, uint32_t n_frames, u
         for (uint32_t c = 0; c < ich; ++c)
             HIPCHK(e, hipMemcpyAsync(e->tile_in + (size_t)c * Ft * n, in + c * plane + (size_t)f0 * n, bytes,
                                      hipMemcpyDeviceToDevice, s));
-        const int rc = launch(e, e->tile_in, e->tile_out, Ft, (uint64_t)Ft * n, s, f0 ? none : ev);
+        const int rc = launch(e, e->tile_in, e->tile_out, Ft, (uint64_t)Ft * n, s, f0 ? none : ev, f0 ? no_tp : tp);
         if (rc) return rc;
         for (uint32_t c = 0; c < och; ++c)
             HIPCHK(e, hipMemcpyAsync(out + c * plane + (size_t)f0 * n, e->tile_out + (size_t)c * Ft * n, bytes,
@@ -916,7 +931,8 @@ static int create_engine(int kind, int device, uint32_t n_inst, uint32_t voices,
     // for the largest packet this engine can produce (up to 256 MiB each; larger on first need)
     const size_t maxw = host::max_packet_words(kind, n_inst, e->hs.n_ev(),
                                                std::max(host::max_segments(kind), host::max_note_segments(kind))) +
-                        host::max_timed_param_words(kind, n_inst);
+                        host::max_timed_param_words(kind, n_inst) +
+                        host::max_timed_instrument_words(kind, n_inst, e->hs.voices);
     for (olfx_engine::Slot &sl : e->slot)
         if (!rc) rc = grow_slot(e, sl, olfx_engine::kCopyBytes / 4, false);
     if (maxw * 4 >= e->copy_bytes && maxw * 4 <= ((size_t)256 << 20))
@@ -1024,6 +1040,14 @@ int olfx_timed_control(olfx_engine *e, const struct olfx_timed_control *rec, uin
     return e ? e->report(e->hs.timed_control(rec, n)) : OLFX_E_ARG;
 }
 
+int olfx_timed_instrument_params(olfx_engine *e, const olfx_timed_param *rec, uint32_t n) {
+    return e ? e->report(e->hs.timed_instrument_params(rec, n)) : OLFX_E_ARG;
+}
+
+int olfx_timed_instrument_control(olfx_engine *e, const struct olfx_timed_control *rec, uint32_t n) {
+    return e ? e->report(e->hs.timed_instrument_control(rec, n)) : OLFX_E_ARG;
+}
+
 int olfx_synth_playing(olfx_engine *e, uint32_t inst, uint8_t *playing) {
     return e ? e->report(e->hs.synth_playing(inst, playing)) : OLFX_E_ARG;
 }
@@ -1063,15 +1087,16 @@ int olfx_process(olfx_engine *e, const float *in, float *out, uint32_t n_frames,
     for (uint32_t f0 = 0; f0 < n_frames;) {
         const uint32_t span = e->hs.span(n_frames - f0);
         VoiceArgs ev{};
+        InstrumentTimed tp{};
         olfx_engine::Slot *sl = nullptr;
-        rc = submit_control(e, s, &ev, &sl, span);
+        rc = submit_control(e, s, &ev, &tp, &sl, span);
         if (rc) return rc;
         if (host_io && fin && f0 == 0) {
             std::memcpy(e->h_in, in, fin * 4);
             const hipError_t r = hipMemcpyAsync(e->d_in, e->h_in, fin * 4, hipMemcpyHostToDevice, s);
             if (r != hipSuccess) rc = e->hip_fail(r, "olfx_process: input copy");
         }
-        if (!rc) rc = run_frames(e, rin, rout ? rout + (size_t)f0 * e->n : nullptr, span, n_frames, s, ev);
+        if (!rc) rc = run_frames(e, rin, rout ? rout + (size_t)f0 * e->n : nullptr, span, n_frames, s, ev, tp);
         launched_on(e, s);
         // the slot is free again once whatever was queued on `s` (the scatter, the kernels) is done --
         // recorded on the error paths too, so a later block never overwrites a packet still being read

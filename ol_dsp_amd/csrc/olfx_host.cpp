@@ -577,6 +577,11 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
 }
 
 void Shadow::derive_record(uint32_t i, uint32_t *w) const {
+    // (an instrument whose last timed record still stands: the whole record, fold_segments derived it)
+    if (!ic_words.empty() && ic_of[i] >= 0) {
+        std::memcpy(w, ic_words.data() + ic_of[i], (size_t)kd->words * 4);
+        return;
+    }
     float p[kMaxParams];
     for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
     for (uint32_t j = 0; j < kd->nparts; ++j) {
@@ -591,6 +596,10 @@ void Shadow::derive_record(uint32_t i, uint32_t *w) const {
 }
 
 void Shadow::derive_voice_record(uint32_t hv, uint32_t *w) const {
+    if (!vc_words.empty() && vc_of[hv] >= 0) {           // (as derive_record: the slot's last timed record stands)
+        std::memcpy(w, vc_words.data() + vc_of[hv], (size_t)kd->vwords * 4);
+        return;
+    }
     const uint32_t p = hv / n, i = hv % n;
     float v[OLFX_VC_NPARAMS];
     for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) v[f] = params[(size_t)(kd->voice0 + p * OLFX_VC_NPARAMS + f) * n + i];
@@ -645,6 +654,20 @@ void Shadow::reset() {
     tc_cache_of.assign(kd->instances == KindDesc::VOICES ? n : 0u, -1);
     tc_cache.clear();
     tc_cached.clear();
+    iparams.clear();
+    ti_vlane.clear();
+    ti_flane.clear();
+    ti_inst.clear();
+    ti_slot.clear();
+    ti_fresh = false;
+    ti_vlast.assign(kit() ? (size_t)voices * n : instruments() ? n : 0u, -1);
+    ti_flast.assign(instruments() ? n : 0u, -1);
+    ic_of.assign(instruments() ? n : 0u, -1);
+    vc_of.assign(kit() ? (size_t)voices * n : 0u, -1);
+    ic_words.clear();
+    ic_list.clear();
+    vc_words.clear();
+    vc_list.clear();
     ev_slot.assign(n_ev(), -1);
     playing.assign((size_t)voices * n, 0);
     dirty_list.clear();
@@ -658,6 +681,8 @@ void Shadow::reset() {
 void Shadow::mark_dirty(uint32_t first, uint32_t count) {
     if (!tc_cache.empty())                                // whatever is written now, a kept timed record is stale
         for (uint32_t k = first; k < first + count; ++k) tc_cache_of[k] = -1;
+    if (!ic_words.empty())
+        for (uint32_t k = first; k < first + count; ++k) ic_of[k] = -1;
     for (uint32_t k = first; k < first + count; ++k)
         if (!dirty_mark[k]) {
             dirty_mark[k] = 1;
@@ -666,6 +691,7 @@ void Shadow::mark_dirty(uint32_t first, uint32_t count) {
 }
 
 void Shadow::mark_vdirty(uint32_t hv) {
+    if (!vc_words.empty()) vc_of[hv] = -1;
     if (!vdirty_mark[hv]) {
         vdirty_mark[hv] = 1;
         vdirty_list.push_back(hv);
@@ -1198,8 +1224,181 @@ int Shadow::timed_control(const struct olfx_timed_control *rec, uint32_t count) 
     return queue_params(mapped.data(), mapped.size());
 }
 
+
+// Timed parameter and control changes of the synths and the drum kit.  A record at frame 0 is olfx_set_param /
+// olfx_control now; a later one stays pending, raw, until the engine reaches its frame (fold_segments, advance):
+// a control is mapped there, under the instrument's topology and the kit's channel2voice of that moment.
+bool Shadow::is_boundary(const TimedInst &r) const {
+    if (r.ctl) return r.ev.control >= CC_DELAY_TIME && r.ev.control <= CC_DELAY_BALANCE && (!kit() || r.ev.pad == OLFX_DK_CHANNEL_RACK);
+    if (kd->topo_field == kNoField || r.p.field < kd->topo_field - OLFX_FR_TOPOLOGY) return false;
+    const uint32_t rf = r.p.field - (kd->topo_field - OLFX_FR_TOPOLOGY);
+    return rf <= OLFX_FR_DELAY_RESONANCE || rf == OLFX_FR_TOPOLOGY;
+}
+
+void Shadow::apply_inst_now(const TimedInst &r) {
+    // (validated when it was queued: neither call refuses it)
+    if (r.ctl) (void)control(&r.ev, 1);
+    else (void)set_range(r.p.inst, 1, r.p.field, 1, &r.p.value);
+}
+
+void Shadow::queue_inst(const std::vector<TimedInst> &recs) {
+    const size_t old = iparams.size();
+    for (const TimedInst &r : recs) {
+        if (r.frame == 0u) apply_inst_now(r);
+        else iparams.push_back(r);
+    }
+    const auto by_frame = [](const TimedInst &x, const TimedInst &y) { return x.frame < y.frame; };
+    std::stable_sort(iparams.begin() + (ptrdiff_t)old, iparams.end(), by_frame);
+    std::inplace_merge(iparams.begin(), iparams.begin() + (ptrdiff_t)old, iparams.end(), by_frame);
+}
+
+int Shadow::timed_instrument_params(const olfx_timed_param *rec, uint32_t count) {
+    if (kd->instances == KindDesc::VOICES) return fail(OLFX_E_KIND, "olfx_timed_instrument_params: the voice kinds take olfx_timed_params");
+    if (!instruments()) return fail(OLFX_E_STATE, "olfx_timed_instrument_params: not a synth or drum kit engine");
+    if (count && !rec) return fail(OLFX_E_ARG, "olfx_timed_instrument_params: null records");
+    std::vector<TimedInst> recs;
+    recs.reserve(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (rec[k].inst >= n || rec[k].field >= n_params) return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u out of range", k);
+        if (const char *why = bad_value(rec[k].field, rec[k].value))
+            return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u: %s", k, why);
+        recs.push_back(TimedInst{rec[k].frame, false, rec[k], olfx_control_event{}});
+    }
+    queue_inst(recs);
+    return OLFX_OK;
+}
+
+int Shadow::timed_instrument_control(const struct olfx_timed_control *rec, uint32_t count) {
+    if (kd->instances == KindDesc::VOICES) return fail(OLFX_E_KIND, "olfx_timed_instrument_control: the voice kinds take olfx_timed_control");
+    if (!instruments()) return fail(OLFX_E_STATE, "olfx_timed_instrument_control: not a synth or drum kit engine");
+    if (count && !rec) return fail(OLFX_E_ARG, "olfx_timed_instrument_control: null records");
+    std::vector<TimedInst> recs;
+    recs.reserve(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        const olfx_control_event &ev = rec[k].ev;
+        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
+            return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (ev.inst >= n) return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: instance out of range", k);
+        // the mapping waits for the frame, so the record is judged under every mapping it can get there: a record
+        // that olfx_control would refuse under one of them is refused now
+        uint32_t fields[2];
+        float vals[2];
+        if (kit() && ev.pad != OLFX_DK_CHANNEL_RACK) {
+            if (ev.source != OLFX_CTL_MIDI && ev.source != OLFX_CTL_HARDWARE) return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u", k);
+            if (voice_cc(ev.control, CcValue{ev.source == OLFX_CTL_MIDI, ev.value, &fields[0], &vals[0]}) == OLFX_OK &&
+                fields[0] != OLFX_FIELD_UPDATE_ONLY)
+                if (const char *why = bad_value(kd->voice0 + fields[0], vals[0]))
+                    return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: %s", k, why);
+        } else {
+            for (uint32_t t = 0; t <= 4u; ++t) {
+                if (!(kd->topologies >> t & 1)) continue;
+                const int hits = route_control(*kd, t, ev.control, ev.source, ev.value, fields, vals);
+                if (hits < 0) return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u", k);
+                for (int h = 0; h < hits; ++h)
+                    if (fields[h] != OLFX_FIELD_UPDATE_ONLY)
+                        if (const char *why = bad_value(fields[h], vals[h]))
+                            return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: %s", k, why);
+            }
+        }
+        recs.push_back(TimedInst{rec[k].frame, true, olfx_timed_param{}, ev});
+    }
+    queue_inst(recs);
+    return OLFX_OK;
+}
+
+// olfx_set_param's bookkeeping (store_param, touched) with logs in place of the dirty lists
+void Shadow::write_quiet(uint32_t inst, uint32_t field, float v, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f) {
+    store_param(field, inst, v);
+    if (field >= kd->voice0 && field < kd->voice_end) {
+        if (!kit()) {                                     // UpdateConfig + Update() of every voice of the instrument
+            configured[inst] = 1;
+            at_v.push_back(inst);
+            ti_inst.push_back(inst);
+            return;
+        }
+        const uint32_t p = (field - kd->voice0) / OLFX_VC_NPARAMS;
+        if (p < voices) {                                 // (a slot past the kit's voices is read by nothing)
+            configured[(size_t)p * n + inst] = 1;
+            at_v.push_back(p * n + inst);
+            ti_slot.push_back(p * n + inst);
+        }
+        return;
+    }
+    at_f.push_back(inst);
+    ti_inst.push_back(inst);
+}
+
+// Shadow::control's fan-out for one event, likewise
+void Shadow::apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f) {
+    if (!r.ctl) {
+        write_quiet(r.p.inst, r.p.field, r.p.value, at_v, at_f);
+        return;
+    }
+    const olfx_control_event &ev = r.ev;
+    if (kit() && ev.pad != OLFX_DK_CHANNEL_RACK) {
+        const uint8_t p = ev.pad < 16 ? chan2voice[(size_t)ev.pad * n + ev.inst] : kNoVoice;
+        if (p == kNoVoice) return;
+        uint32_t f = 0;
+        float v = 0.f;
+        if (voice_cc(ev.control, CcValue{ev.source == OLFX_CTL_MIDI, ev.value, &f, &v}) != OLFX_OK) return;
+        if (f == OLFX_FIELD_UPDATE_ONLY) {
+            configured[(size_t)p * n + ev.inst] = 1;
+            at_v.push_back(p * n + ev.inst);
+            ti_slot.push_back(p * n + ev.inst);
+        } else {
+            write_quiet(ev.inst, kd->voice0 + p * OLFX_VC_NPARAMS + f, v, at_v, at_f);
+        }
+        return;
+    }
+    const uint32_t topology = kd->topo_field == kNoField ? 0u : (uint32_t)params[(size_t)kd->topo_field * n + ev.inst];
+    uint32_t fields[2];
+    float vals[2];
+    const int hits = route_control(*kd, topology, ev.control, ev.source, ev.value, fields, vals);
+    for (int h = 0; h < hits; ++h) {
+        if (fields[h] == OLFX_FIELD_UPDATE_ONLY) {        // Update() with unchanged members
+            if (!kit()) {
+                configured[ev.inst] = 1;
+                at_v.push_back(ev.inst);
+            }
+            ti_inst.push_back(ev.inst);
+        } else {
+            write_quiet(ev.inst, fields[h], vals[h], at_v, at_f);
+        }
+    }
+}
+
+uint32_t timed_instrument_cap(int kind, uint32_t n, uint32_t voices) {
+    const KindDesc &kd = kind_desc(kind);
+    if (kd.instances != KindDesc::INSTRUMENTS) return 0;
+    return kd.voice_slots ? voices * n : n;
+}
+
 uint32_t Shadow::span(uint32_t n_frames) const {
     uint32_t segs = 1, last = 0;                          // segment 0 starts at frame 0, events or none
+    if (has_timed_inst(n_frames)) {
+        // note times and record times in one ascending walk (all are past frame 0)
+        const uint32_t none = 0xFFFFFFFFu;
+        const size_t cap = timed_instrument_cap(kind, n, voices);
+        size_t ke = 0, kp = 0, recs = 0;
+        for (;;) {
+            const uint32_t te = ke < timed.size() ? timed[ke].frame : none, tp = kp < iparams.size() ? iparams[kp].frame : none;
+            const uint32_t t = te < tp ? te : tp;
+            if (t >= n_frames) return n_frames;
+            if (segs == kSegCap) return t;
+            if (tp == t) {
+                size_t c = 0;
+                for (; kp < iparams.size() && iparams[kp].frame == t; ++kp, ++c)
+                    if (is_boundary(iparams[kp])) return t;   // the next launch starts here, with it at frame 0
+                c = c < cap ? c : cap;                    // (a time changes at most `cap` lanes, however many records)
+                if (recs + c > cap) return t;             // (never a launch's first time: c <= cap)
+                recs += c;
+            }
+            while (ke < timed.size() && timed[ke].frame == t) ++ke;
+            ++segs;
+        }
+    }
     if (!has_timed_params(n_frames)) {
         for (const olfx_timed_event &t : timed) {
             if (t.frame >= n_frames) break;
@@ -1252,6 +1451,14 @@ void Shadow::advance(uint32_t span_) {
         }
     }
     tparams.erase(tparams.begin(), tparams.begin() + (ptrdiff_t)q);
+    if (!iparams.empty()) {                               // (applying one can queue nothing: index, not iterate)
+        size_t qi = 0;
+        for (TimedInst &r : iparams) r.frame = r.frame > span_ ? r.frame - span_ : 0u;
+        while (qi < iparams.size() && !iparams[qi].frame) ++qi;
+        const std::vector<TimedInst> due(iparams.begin(), iparams.begin() + (ptrdiff_t)qi);
+        iparams.erase(iparams.begin(), iparams.begin() + (ptrdiff_t)qi);
+        for (const TimedInst &r : due) apply_inst_now(r);
+    }
     size_t k = 0;
     for (olfx_timed_event &t : timed) {
         t.frame = t.frame > span_ ? t.frame - span_ : 0u;
@@ -1417,6 +1624,13 @@ void Shadow::fold_segments(uint32_t span_) {
     tc_first.assign(1, 0u);
     pre_valid = false;
     tc_fresh = true;
+    ti_vlane.clear();
+    ti_flane.clear();
+    ti_fresh = false;
+    if (has_timed_inst(span_)) {
+        fold_instrument_segments(span_);
+        return;
+    }
     if (has_timed_params(span_)) {
         const size_t m = dirty_list.size(), W = kd->words;
         pre_words.resize(m * W);
@@ -1474,6 +1688,121 @@ void Shadow::fold_segments(uint32_t span_) {
         k = k1;
     }
     timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+}
+
+// The instrument kinds with timed records: a time's records are applied to the shadow in queueing order, a control
+// mapped there, ahead of routing that time's notes; every instrument (a kit: voice slot) whose voice fields they
+// touch gets one voice record for the segment, every instrument whose rack fields they touch one rack record.  The
+// dirty instances' frame-0 records are derived first (pre_words, pre_vwords), and what the records changed is
+// listed with its last record (ti_inst, ti_slot) for fill_records to put back on the dirty lists.
+void Shadow::fold_instrument_segments(uint32_t span_) {
+    const size_t m = dirty_list.size(), W = kd->words, m2 = vdirty_list.size(), W2 = kd->vwords;
+    pre_words.resize(m * W);
+    for (size_t r = 0; r < m; ++r) derive_record(m == n ? (uint32_t)r : dirty_list[r], pre_words.data() + r * W);
+    pre_vwords.resize(m2 * W2);
+    for (size_t r = 0; r < m2; ++r) derive_voice_record(vdirty_list[r], pre_vwords.data() + r * W2);
+    pre_valid = true;
+    // (the previous launch's kept records have served: what is derived from here on is derived afresh)
+    for (const uint32_t i : ic_list) ic_of[i] = -1;
+    for (const uint32_t hv : vc_list) vc_of[hv] = -1;
+    ic_words.clear();
+    ic_list.clear();
+    vc_words.clear();
+    vc_list.clear();
+    ti_inst.clear();
+    ti_slot.clear();
+    ti_vwords.clear();
+    ti_fwords.clear();
+    ti_ffull.clear();
+    fold_events();                                        // segment 0: the frame-0 queue
+    ti_vfirst.assign(2, 0u);
+    ti_ffirst.assign(2, 0u);
+    const uint32_t none = 0xFFFFFFFFu;
+    size_t k = 0, q = 0;
+    std::vector<uint32_t> at_v, at_f;
+    uint32_t fw[FRC_N];
+    float p[std::max<uint32_t>(OLFX_FR_NPARAMS, OLFX_VC_NPARAMS)];
+    auto uniq = [](std::vector<uint32_t> &v) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    };
+    for (;;) {
+        const uint32_t te = k < timed.size() ? timed[k].frame : none, tp = q < iparams.size() ? iparams[q].frame : none;
+        const uint32_t t = te < tp ? te : tp;
+        if (t >= span_) break;
+        seg_frame.push_back(t);
+        at_v.clear();
+        at_f.clear();
+        for (; q < iparams.size() && iparams[q].frame == t; ++q) apply_inst_quiet(iparams[q], at_v, at_f);
+        uniq(at_v);
+        uniq(at_f);
+        for (const uint32_t v : at_v) {                   // a synth: the instrument; a kit: hv = slot * n + kit
+            const uint32_t slot = kit() ? v / n : 0u, i = kit() ? v % n : v;
+            for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) p[f] = params[(size_t)(kd->voice0 + slot * OLFX_VC_NPARAMS + f) * n + i];
+            ti_vwords.resize(ti_vwords.size() + VCC_N);
+            derive_voice(p, configured[v] != 0, kd->moog, sr, ti_vwords.data() + ti_vwords.size() - VCC_N);
+            ti_vlast[v] = (int32_t)ti_vlane.size();
+            ti_vlane.push_back(kit() ? slot * npad + i : i);
+        }
+        const uint32_t rack0 = kd->topo_field - OLFX_FR_TOPOLOGY;
+        for (const uint32_t i : at_f) {
+            for (uint32_t f = 0; f < OLFX_FR_NPARAMS; ++f) p[f] = params[(size_t)(rack0 + f) * n + i];
+            derive_fxrack(p, sr, fw);
+            ti_fwords.insert(ti_fwords.end(), fw + FRC_RBAL, fw + FRC_RBAL + TIF_N);
+            ti_ffull.insert(ti_ffull.end(), fw, fw + FRC_N);
+            ti_flast[i] = (int32_t)ti_flane.size();
+            ti_flane.push_back(i);
+        }
+        size_t k1 = k;
+        while (k1 < timed.size() && timed[k1].frame == t) ++k1;
+        routed.clear();                                   // parameters precede the notes of their frame
+        for (size_t j = k; j < k1; ++j) route_note(routed, timed[j].ev);
+        fold_one(routed.data(), routed.size(), sizeof(olfx_voice_event));
+        seg_first.push_back((uint32_t)folded.size());
+        ti_vfirst.push_back((uint32_t)ti_vlane.size());
+        ti_ffirst.push_back((uint32_t)ti_flane.size());
+        k = k1;
+    }
+    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+    iparams.erase(iparams.begin(), iparams.begin() + (ptrdiff_t)q);
+    uniq(ti_inst);
+    uniq(ti_slot);
+    // the last records, whole: an instrument's (a slot's) latest voice record and latest rack record of this fold are
+    // its voice and rack words as the launch leaves them -- nothing is derived a second time; the parts no record of
+    // the fold covers are derived here
+    ti_inst_words.resize(ti_inst.size() * W);
+    float all[kMaxParams];
+    for (size_t r = 0; r < ti_inst.size(); ++r) {
+        const uint32_t i = ti_inst[r];
+        uint32_t *w = ti_inst_words.data() + r * W;
+        bool have = false;
+        for (uint32_t j = 0; j < kd->nparts; ++j) {
+            const Part &pt = kd->parts[j];
+            const Component &c = kComponents[pt.comp];
+            if (pt.comp == CP_VOICE && ti_vlast[i] >= 0) {
+                std::memcpy(w, ti_vwords.data() + (size_t)ti_vlast[i] * VCC_N, (size_t)VCC_N * 4);
+            } else if (pt.comp == CP_RACK && ti_flast[i] >= 0) {
+                std::memcpy(w, ti_ffull.data() + (size_t)ti_flast[i] * FRC_N, (size_t)FRC_N * 4);
+            } else {
+                if (!have)
+                    for (uint32_t f = 0; f < n_params; ++f) all[f] = params[(size_t)f * n + i];
+                have = true;
+                c.derive(all + pt.field0, *this, i, w);
+            }
+            w += c.words;
+        }
+    }
+    ti_slot_words.resize(ti_slot.size() * W2);
+    for (size_t r = 0; r < ti_slot.size(); ++r) {             // (a listed slot has a voice record in this fold)
+        const uint32_t hv = ti_slot[r];
+        uint32_t *w = ti_slot_words.data() + r * W2;
+        std::memcpy(w, ti_vwords.data() + (size_t)ti_vlast[hv] * VCC_N, (size_t)VCC_N * 4);
+        sample_record(hv % n * voices + hv / n, w + VCC_N);
+    }
+    for (const uint32_t i : ti_inst) ti_flast[i] = -1;
+    if (kit()) for (const uint32_t hv : ti_slot) ti_vlast[hv] = -1;
+    else for (const uint32_t i : ti_inst) ti_vlast[i] = -1;
+    ti_fresh = true;
 }
 
 // `count` events `stride` bytes apart
@@ -1555,7 +1884,7 @@ void Shadow::write_events(uint32_t *fix) {
 }
 
 PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev, size_t m2, uint32_t W2,
-                       uint32_t n_seg, size_t n_tc) {
+                       uint32_t n_seg, size_t n_tc, size_t n_iv, size_t n_if, uint32_t gv, uint32_t gf) {
     PacketPlan pl;
     pl.dense = m == n;                                   // every instance: no instance list
     pl.o_inst = 0;
@@ -1579,6 +1908,17 @@ PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_mo
         pl.o_tc = up4(pl.o_tcb + pl.n_seg * (size_t)(((n_ev ? n_ev : n) + 63u) / 64u));
         pl.words = pl.o_tc + (size_t)VCC_N * n_tc;
     }
+    if (evs && pl.n_seg > 1 && n_iv + n_if) {             // timed instrument records: two tables, two record arrays
+        pl.n_iv = n_iv;
+        pl.n_if = n_if;
+        pl.gv = gv;
+        pl.gf = gf;
+        pl.o_ivt = up4(pl.words);
+        pl.o_ift = pl.o_ivt + 4 * pl.n_seg * (size_t)gv;
+        pl.o_iv = pl.o_ift + 4 * pl.n_seg * (size_t)gf;
+        pl.o_if = up4(pl.o_iv + (size_t)VCC_N * n_iv);
+        pl.words = pl.o_if + (size_t)TIF_N * n_if;
+    }
     return pl;
 }
 
@@ -1586,6 +1926,37 @@ size_t max_timed_param_words(int kind, uint32_t n) {
     if (kind_desc(kind).instances != KindDesc::VOICES) return 0;
     // the section's alignment (up to 3 words), the base table of a full launch rounded up to the records', n records
     return 3 + up4((size_t)kSegCap * ((n + 63u) / 64u)) + (size_t)VCC_N * n;
+}
+
+size_t max_timed_instrument_words(int kind, uint32_t n, uint32_t voices) {
+    const size_t cap = timed_instrument_cap(kind, n, voices);
+    if (!cap) return 0;
+    const size_t g = (n + 63u) / 64u, gv = kind_desc(kind).voice_slots ? voices * g : g;
+    // the section's alignment, both tables of a full launch, `cap` voice records, alignment, `cap` rack records
+    return 3 + 4 * (size_t)kSegCap * (gv + g) + (size_t)VCC_N * cap + 3 + (size_t)TIF_N * cap;
+}
+
+void Shadow::write_timed_inst(const PacketPlan &pl, uint32_t *buf) const {
+    // a table: per segment and group, the lanes that have a record and the number of the first (ascending lanes:
+    // a group's run starts where the group before it ends)
+    auto table = [&](uint32_t *tab, size_t groups, const std::vector<uint32_t> &lane, const std::vector<uint32_t> &first) {
+        std::memset(tab, 0, 4 * pl.n_seg * groups * 4);
+        for (size_t s = 0; s + 1 < first.size() && s < pl.n_seg; ++s) {
+            size_t r = first[s];
+            for (size_t g = 0; g < groups; ++g) {
+                uint32_t *e = tab + 4 * (s * groups + g);
+                e[2] = (uint32_t)r;
+                for (; r < first[s + 1] && (lane[r] >> 6) == g; ++r) e[(lane[r] & 63u) >> 5] |= 1u << (lane[r] & 31u);
+            }
+        }
+    };
+    table(buf + pl.o_ivt, pl.gv, ti_vlane, ti_vfirst);
+    table(buf + pl.o_ift, pl.gf, ti_flane, ti_ffirst);
+    for (size_t r = 0; r < pl.n_iv; ++r)
+        for (uint32_t w = 0; w < VCC_N; ++w) buf[pl.o_iv + (size_t)w * pl.n_iv + r] = ti_vwords[r * VCC_N + w];
+    for (size_t w = pl.o_iv + (size_t)VCC_N * pl.n_iv; w < pl.o_if; ++w) buf[w] = 0u;
+    for (size_t r = 0; r < pl.n_if; ++r)
+        for (uint32_t w = 0; w < TIF_N; ++w) buf[pl.o_if + (size_t)w * pl.n_if + r] = ti_fwords[r * TIF_N + w];
 }
 
 void Shadow::write_timed_coefs(const PacketPlan &pl, uint32_t *buf) const {
@@ -1651,6 +2022,7 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
     dirty_list.clear();
     // the voices the launch's timed records change stay dirty: the device arrays get their last record ahead of
     // the next launch (the kernels never write the coefficient arrays)
+    const bool had_pre = pre_valid && instruments();
     pre_valid = false;
     if (!tc_cache.empty()) {                              // the previous launch's voices alone: nothing else is set
         for (const uint32_t i : tc_cached) tc_cache_of[i] = -1;
@@ -1674,11 +2046,37 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
         for (size_t r = 0; r < pl.m2; ++r) {
             const uint32_t hv = vdirty_list[r];
             buf[pl.o_inst2 + r] = hv / n * npad + hv % n;
-            derive_voice_record(hv, h_words.data());
+            if (had_pre) std::memcpy(h_words.data(), pre_vwords.data() + r * W2, (size_t)W2 * 4);   // frame 0's
+            else derive_voice_record(hv, h_words.data());
             for (uint32_t w = 0; w < W2; ++w) buf[pl.o_val2 + (size_t)w * pl.m2 + r] = h_words[w];
             vdirty_mark[hv] = 0;
         }
         vdirty_list.clear();
+    }
+    // timed instrument records: the previous launch's kept records have served; this launch's instruments and voice
+    // slots go back on the lists with their last record (once per fold, as above)
+    if (!ic_words.empty() || !vc_words.empty()) {
+        for (const uint32_t i : ic_list) ic_of[i] = -1;
+        for (const uint32_t hv : vc_list) vc_of[hv] = -1;
+        ic_words.clear();
+        ic_list.clear();
+        vc_words.clear();
+        vc_list.clear();
+    }
+    if (ti_fresh) {
+        for (size_t r = 0; r < ti_inst.size(); ++r) mark_dirty(ti_inst[r], 1);
+        for (size_t r = 0; r < ti_slot.size(); ++r) mark_vdirty(ti_slot[r]);
+        ic_words.swap(ti_inst_words);
+        ic_list.swap(ti_inst);
+        vc_words.swap(ti_slot_words);
+        vc_list.swap(ti_slot);
+        for (size_t r = 0; r < ic_list.size(); ++r) ic_of[ic_list[r]] = (int32_t)(r * W);
+        for (size_t r = 0; r < vc_list.size(); ++r) vc_of[vc_list[r]] = (int32_t)(r * kd->vwords);
+        ti_inst_words.clear();
+        ti_inst.clear();
+        ti_slot_words.clear();
+        ti_slot.clear();
+        ti_fresh = false;
     }
     if (pitch_changed && rf.changed()) rf_materialise = true;
 }

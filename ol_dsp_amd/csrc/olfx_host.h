@@ -99,6 +99,15 @@ Segments voice_segments(int kind);           // a kit kind's record per voice sl
 // timed parameters (n_tc >= 1 coefficient records in the launch's segments), after the start frames: the base
 // table [n_seg][groups] (the launch-wide number of a 64-voice group's first record of a segment) | the records,
 // field-major [VCC_N][n_tc], segment by segment and by voice index inside a segment
+// timed instrument parameters (the synths and the drum kit; n_iv + n_if >= 1 records in the launch's segments),
+// after the start frames, 16-B aligned: the voice table [n_seg][gv] and the rack table [n_seg][gf], four words an
+// entry {lane mask low, lane mask high, base, 0} -- the 64 lanes of a group that have a record in the segment and
+// the launch-wide number of the first of them, so a lane's record is base + its rank among the mask's lower bits |
+// the voice records, field-major [VCC_N][n_iv] | the rack records, field-major [TIF_N][n_if] (olfx_layout.h TIF_*:
+// the six words the F role reads).  A synth's group is 64 instruments (gv = gf = npad / 64): its voice record is
+// the instrument's and reaches all its voices.  A kit's voice record is a voice slot's: group p (npad / 64) + g,
+// lane = kit (gv = voices npad / 64); its rack record is the kit's.  An instrument changed at a time has a voice
+// record, a rack record or both there; records run segment by segment and by lane inside a segment.
 struct PacketPlan {
     bool dense;
     size_t o_inst, o_val, o_ev, words;
@@ -107,13 +116,17 @@ struct PacketPlan {
     // a kit kind's second section, ahead of the events: the m2 changed voice slots (device slots p * npad + kit,
     // always listed) and their records [W2][m2]
     size_t m2 = 0, o_inst2 = 0, o_val2 = 0;
+    // timed instrument records: the voice and rack tables, the voice and rack records
+    size_t n_iv = 0, n_if = 0, gv = 0, gf = 0, o_ivt = 0, o_ift = 0, o_iv = 0, o_if = 0;
 };
 // n instances of which m changed, W words per record, `evs`: an event section with n_more
 // overflow records for n_ev voice slots (0: the n instances are the voices)
 // n_seg: the event section's segments (timed events)
 // n_tc: the launch's timed coefficient records (olfx_timed_params; 0: no such section)
+// n_iv, n_if: the launch's timed instrument records (voice, rack) over tables of gv and gf groups a segment
 PacketPlan plan_packet(uint32_t n, size_t m, uint32_t W, bool evs, uint32_t n_more, uint32_t n_ev = 0, size_t m2 = 0,
-                       uint32_t W2 = 0, uint32_t n_seg = 1, size_t n_tc = 0);
+                       uint32_t W2 = 0, uint32_t n_seg = 1, size_t n_tc = 0, size_t n_iv = 0, size_t n_if = 0,
+                       uint32_t gv = 0, uint32_t gf = 0);
 // The largest packet an engine can produce: every instance's coefficients and, for voices, an
 // event for every voice (plan_packet's layout, rounded up); n_ev as above (the synth's voice slots).  A kit
 // kind: every kit's record, every voice slot's record and an event per voice.  n_seg: the segments of a
@@ -123,6 +136,11 @@ size_t max_packet_words(int kind, uint32_t n, uint32_t n_ev = 0, uint32_t n_seg 
 // launch carries at most n coefficient records over all its segments (Shadow::span), so the worst packet grows
 // by one full voice-coefficient upload and the base table, not by kSegCap uploads.
 size_t max_timed_param_words(int kind, uint32_t n);
+// The same for olfx_timed_instrument_params (the synths and the drum kit, else 0): both tables of a full launch and
+// timed_instrument_cap voice records and as many rack records.  An engine sizes its packet slots by the sum of both.
+size_t max_timed_instrument_words(int kind, uint32_t n, uint32_t voices);
+// the raw records one launch takes (Shadow::span): n, a kit voices x n -- what one time can change at the most
+uint32_t timed_instrument_cap(int kind, uint32_t n, uint32_t voices);
 // the segments one launch of a kind can take: kSegCap for the kinds olfx_timed_events accepts, else 1
 uint32_t max_segments(int kind);
 // ... for the kinds olfx_timed_notes accepts (the synths and the drum kit): kSegCap, else 1.  An engine's packet
@@ -130,6 +148,14 @@ uint32_t max_segments(int kind);
 uint32_t max_note_segments(int kind);
 
 struct Folded { uint32_t inst, op, freq, pad; };
+// A pending olfx_timed_instrument_params / olfx_timed_instrument_control record, held raw: a control is mapped when
+// the engine reaches its frame (the topology and the kit's channel2voice in force there)
+struct TimedInst {
+    uint32_t frame;
+    bool ctl;
+    olfx_timed_param p;                   // !ctl
+    olfx_control_event ev;                // ctl
+};
 
 // ---- sample voices: the bank's layout and each voice's Sample (olfx_sample_bank / olfx_sample_voices) ----
 // A validated bank: where each sample goes in the device allocation (kSmAlign-aligned starts, a
@@ -221,6 +247,28 @@ struct Shadow {
     // tc_cached: the voices that have an entry (a packet without kept records touches none of this)
     std::vector<int32_t> tc_cache_of;
     std::vector<uint32_t> tc_cache, tc_cached;
+    // olfx_timed_instrument_params / olfx_timed_instrument_control (the synths and the drum kit): the records past
+    // frame 0, raw, stably ordered by frame in one queueing order for both calls
+    std::vector<TimedInst> iparams;
+    // fold_segments: the launch's voice records -- the lane of each (a synth: the instrument; a kit: the device voice
+    // slot p * npad + kit), segment s being ti_vlane[ti_vfirst[s] .. ti_vfirst[s + 1]), ascending inside a segment,
+    // and their words [records][VCC_N] -- and its rack records likewise (lane = instrument, [records][TIF_N])
+    std::vector<uint32_t> ti_vlane, ti_vfirst, ti_vwords, ti_flane, ti_ffirst, ti_fwords;
+    // ... each rack record's whole FRC_N words, and during a fold an instrument's (a kit: voice slot hv's) latest voice
+    // record and an instrument's latest rack record (-1: none; all -1 between folds)
+    std::vector<uint32_t> ti_ffull;
+    std::vector<int32_t> ti_vlast, ti_flast;
+    // ... and what the launch's records changed: the instruments and (a kit) the voice slots hv = p * n + kit, each
+    // once, with the whole coefficient record of each as the launch's last time leaves it ([.][kd->words],
+    // [.][kd->vwords]).  fill_records puts them back on the dirty lists and keeps the records (ic_* / vc_*: as
+    // tc_cache, by instrument and by voice slot), so the scatter ahead of the next launch derives nothing twice;
+    // mark_dirty / mark_vdirty forget an entry.  A packet without such records touches none of this.
+    std::vector<uint32_t> ti_inst, ti_inst_words, ti_slot, ti_slot_words;
+    bool ti_fresh = false;
+    std::vector<int32_t> ic_of, vc_of;
+    std::vector<uint32_t> ic_words, ic_list, vc_words, vc_list;
+    // the dirty voice slots' records as frame 0 has them (a kit; pre_words' twin, [m2][vwords])
+    std::vector<uint32_t> pre_vwords;
     // fold_events / fold_segments: one record per voice and segment, segment by segment and by first
     // appearance; segment s is folded[seg_first[s] .. seg_first[s + 1]) and starts at frame seg_frame[s]
     std::vector<Folded> folded;
@@ -277,16 +325,27 @@ struct Shadow {
     int timed_notes(const olfx_timed_note *ev, uint32_t count);
     int timed_params(const olfx_timed_param *rec, uint32_t count);
     int timed_control(const struct olfx_timed_control *rec, uint32_t count);
+    // the synths and the drum kit: records held raw, applied (and a control mapped) at their frame
+    int timed_instrument_params(const olfx_timed_param *rec, uint32_t count);
+    int timed_instrument_control(const struct olfx_timed_control *rec, uint32_t count);
     // The frames of the next launch of a block of n_frames: all of them, unless more than kSegCap distinct
     // times lie in it (frame 0 included, with or without events; a time is an event's or a timed parameter
     // record's) -- then up to the first time that does not fit.  Timed parameters bound the launch a second
     // way: its coefficient records (one per voice changed at a time) number at most n, so the launch ends
     // before the time whose records would exceed that; one time alone always fits.
+    // Timed instrument records count as times too, and bound the launch twice more: it ends before a time that
+    // holds a boundary record (is_boundary), which so lands at the next launch's frame 0, and before the time whose
+    // raw records would make more than timed_instrument_cap of them (a time's own count at most the cap).
     uint32_t span(uint32_t n_frames) const;
+    // a pending instrument record that the D role's launch-constant geometry rules out inside a launch: a write to
+    // the delay fields or the topology, or a control that can map to one (CCs 35-39 to the rack)
+    bool is_boundary(const TimedInst &r) const;
     // whether a launch of `span` frames has events
     bool has_events(uint32_t span_) const {
-        return !events.empty() || (!timed.empty() && timed.front().frame < span_) || has_timed_params(span_);
+        return !events.empty() || (!timed.empty() && timed.front().frame < span_) || has_timed_params(span_) ||
+               has_timed_inst(span_);
     }
+    bool has_timed_inst(uint32_t span_) const { return !iparams.empty() && iparams.front().frame < span_; }
     // ... has timed parameter records (they are past frame 0: the launch is segmented)
     bool has_timed_params(uint32_t span_) const { return !tparams.empty() && tparams.front().frame < span_; }
     // After a launch of `span` frames: the pending events' frames count from the next launch (an event at
@@ -324,7 +383,8 @@ struct Shadow {
     uint32_t n_chunks(uint32_t span_, uint32_t chunk) const;
     PacketPlan plan(bool evs) const {
         return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords,
-                           evs ? n_seg() : 1u, evs ? tc_inst.size() : 0u);
+                           evs ? n_seg() : 1u, evs ? tc_inst.size() : 0u, evs ? ti_vlane.size() : 0u,
+                           evs ? ti_flane.size() : 0u, kit() ? voices * (npad >> 6) : npad >> 6, npad >> 6);
     }
     // The plan's instance list and field-major records into `buf`; clears the dirty list.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
@@ -336,6 +396,8 @@ struct Shadow {
     void write_events(uint32_t *fix);
     // The timed coefficient section (pl.n_tc >= 1): the base table and the records into `buf`.
     void write_timed_coefs(const PacketPlan &pl, uint32_t *buf) const;
+    // The timed instrument section (pl.n_iv + pl.n_if >= 1): both tables and both record arrays into `buf`.
+    void write_timed_inst(const PacketPlan &pl, uint32_t *buf) const;
 
 private:
     int fail(int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
@@ -364,6 +426,14 @@ private:
     // Update()) of that voice; `mark`: onto the dirty list as well
     void apply_param(const olfx_timed_param &r, bool mark);
     int queue_params(const olfx_timed_param *rec, size_t count);
+    // validated instrument records: frame 0 now (set_range / control), the rest onto iparams
+    void queue_inst(const std::vector<TimedInst> &recs);
+    void apply_inst_now(const TimedInst &r);
+    // fold_segments: one record on params / configured at its frame without touching the dirty lists; the
+    // instruments it touched onto ti_inst, what needs a voice or rack record at this time onto at_v / at_f
+    void apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f);
+    void write_quiet(uint32_t inst, uint32_t field, float v, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f);
+    void fold_instrument_segments(uint32_t span_);
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
         return kd->instances == KindDesc::VOICES || (n_fields && field0 < kd->voice_end && field0 + n_fields > kd->voice0);

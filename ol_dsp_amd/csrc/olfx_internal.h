@@ -338,6 +338,21 @@ inline bool instrument_args_ok(const InstrumentArgs &a, uint32_t max_voices) {
            (a.n_seg <= 1u || (a.n_seg <= kSegCap && a.seg && a.ev));          // a segmented launch's table is there
 }
 
+// Timed instrument parameters (olfx_timed_instrument_params; the *_seg kernels alone take them, in an argument block
+// of their own -- the unsegmented kernels' arguments are what they were).  The packet's section (host::PacketPlan):
+// vtab [n_seg][gv] and ftab [n_seg][npad / 64], an entry {lane mask low, high, base, 0}: the lanes of a 64-lane
+// group that have a record at segment s's start, the first of them record `base`, the others by rank among the
+// mask's lower bits.  Voice records vrec, field-major [VCC_N][n_v]: a synth's group is 64 instruments (gv =
+// npad / 64; the record reaches every voice of the instrument), a kit's voice slot p's kits (gv = voices npad / 64,
+// group p (npad / 64) + g).  Rack records frec, field-major [TIF_N][n_f], lane = instrument.  vtab == nullptr: none.
+struct InstrumentTimed {
+    const uint4 *vtab;
+    const uint4 *ftab;
+    const float *vrec;
+    const uint32_t *frec;
+    uint32_t n_v, n_f, gv;
+};
+
 // The synth (synth.hip): `voices` MoogFilter SynthVoices per instrument, their Polyvoice sum, the
 // rack's topology 1, in one launch.  The voice coefficients are the instrument's (Polyvoice fans
 // every setter out to all its voices).
@@ -346,7 +361,17 @@ inline bool instrument_args_ok(const InstrumentArgs &a, uint32_t max_voices) {
 struct SynthArgs : InstrumentArgs {
     uint32_t svf;               // 1: synth_svf_block_v1
 };
-hipError_t launch_synth(const SynthArgs &a, hipStream_t s);
+// what a launch requires of the section: none, or a segmented launch with both tables, the record arrays that have
+// records, and the table width of the kind (per_slot: a kit)
+inline bool instrument_timed_ok(const InstrumentArgs &a, const InstrumentTimed &t, bool per_slot) {
+    if (!t.vtab) return true;
+    return a.n_seg > 1u && t.ftab && (!t.n_v || t.vrec) && (!t.n_f || t.frec) &&
+           t.gv == (per_slot ? a.voices : 1u) * (a.npad >> 6);
+}
+struct SynthSegArgs : SynthArgs {
+    InstrumentTimed tp;
+};
+hipError_t launch_synth(const SynthSegArgs &a, hipStream_t s);
 
 // The drum kit (drumkit.hip): `voices` sample voices per kit, their VoiceMap sum in the order the host
 // derived from the kit's map (DKC_ORDER), the rack at each kit's topology (0 or 1), in one launch.  A voice
@@ -357,7 +382,10 @@ struct DrumkitArgs : InstrumentArgs {
     const float *bank;          // bank_bytes bytes (nullptr / 0: no bank)
     uint32_t bank_bytes;
 };
-hipError_t launch_drumkit(const DrumkitArgs &a, hipStream_t s);
+struct DrumkitSegArgs : DrumkitArgs {
+    InstrumentTimed tp;
+};
+hipError_t launch_drumkit(const DrumkitSegArgs &a, hipStream_t s);
 
 hipError_t launch_dattorro(const DattorroArgs &a, int net, hipStream_t s);
 hipError_t launch_chain(const ChainArgs &a, hipStream_t s);

@@ -213,5 +213,9 @@ enum {
     FRC_N
 };
 enum { FRS_DLOW = 0, FRS_DBAND, FRS_FLOW, FRS_FBAND, FRS_N };
+// A timed rack record of the instrument kernels (olfx_timed_instrument_params): the words the F role reads, in
+// FRC order -- word TIF_k is FRC_RBAL + k.  The delay words and the topology are the launch's (the D role).
+enum { TIF_RBAL = 0, TIF_FFREQ, TIF_FDAMP, TIF_FDRIVE, TIF_FTYPE, TIF_MASTER, TIF_N };
+static_assert(FRC_MASTER - FRC_RBAL + 1 == TIF_N, "the F role's words are consecutive");
 
 }  // namespace olfx

@@ -70,8 +70,15 @@ struct SySvfVoice : VoiceEnvs {
 // SEG (synth_block_v1_seg, synth_svf_block_v1_seg; olfx_timed_notes): the launch's frames are a.n_seg segments
 // with note events of their own; the V waves split their chunks at the segment starts (sy::role_v), D and F are
 // the same code.  The per-sample voice functions make the pieces bit-exact with a launch per segment.
-template <bool SVF, bool SEG>
-__global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
+// TP (synth_block_v1_seg_tp, synth_svf_block_v1_seg_tp; a.tp; olfx_timed_instrument_params; a SEG launch whose packet
+// has timed records -- one without runs the SEG kernel as it was): the voice coefficients are loop-carried -- at a
+// segment start a lane whose instrument has a voice record there takes amp_amt .. K (and kc) from it, ahead of the
+// segment's events, and remembers the record: voice_envs_restart reads the envelope words of the instrument's
+// latest record, the device array's until the first.  The kernels never write the coefficient arrays.  F takes
+// the rack records (sy::role_f).
+template <bool SVF, bool SEG, bool TP = false>
+__global__ __launch_bounds__(sy::kThreads) void synth_block(std::conditional_t<TP, SynthSegArgs, SynthArgs> a) {
+    static_assert(SEG || !TP, "timed records come with segments");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const sy::Wg b = sy::enter(a, lds);
     const uint32_t n = b.n, P = b.P;
@@ -82,11 +89,12 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
         const float *c = a.vc_coef;                        // the instrument's: shared by its voices
         float *s = a.vc_state;
 
-        const float amp_amt = c[VCC_AMP_AMT * n + i], port_c = c[VCC_PORT_COEF * n + i];
-        const float inv_sr = c[VCC_INV_SR * n + i];
-        const float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
-        const float drive = c[VCC_DRIVE * n + i], fc_max = c[VCC_FC_MAX * n + i];
-        const float K = c[VCC_LADDER_K * n + i];           // the Svf voice: VCC_DAMP_RES (the same word)
+        // (SEG: loop-carried -- a segment with a voice record replaces them)
+        float amp_amt = c[VCC_AMP_AMT * n + i], port_c = c[VCC_PORT_COEF * n + i];
+        float inv_sr = c[VCC_INV_SR * n + i];
+        float cutoff = c[VCC_CUTOFF * n + i], fenv_amt = c[VCC_FENV_AMT * n + i];
+        float drive = c[VCC_DRIVE * n + i], fc_max = c[VCC_FC_MAX * n + i];
+        float K = c[VCC_LADDER_K * n + i];                 // the Svf voice: VCC_DAMP_RES (the same word)
         SvfVoiceCoef kc{};
         if constexpr (SVF)                                 // as voice_role_env / voice_role_freq form them
             kc = SvfVoiceCoef{0.5f * amp_amt, port_c, inv_sr, cutoff, fenv_amt, fc_max, drive, K,
@@ -149,7 +157,7 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
                 for (uint32_t k = 0; k < m; ++k) tick(k);
             }
         };
-        if constexpr (SEG) {
+        if constexpr (SEG && !TP) {
             // a segment's events on the live voice: the gate and the envelopes, and NoteOn's pitch
             auto start = [&](V &v, uint32_t, const VoiceEv &ev) {
                 voice_envs_restart(v, ev, c, n, i);
@@ -159,6 +167,32 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
                 }
             };
             sy::role_v<V, true>(b, load, run, store, &a, start);
+        } else if constexpr (TP) {
+            // ... and ahead of them the instrument's voice record of the segment, if it has one
+            // (both voices of a wave get the instrument's record: the second reload repeats the first)
+            uint32_t crec = kNoCoef;                       // the instrument's latest voice record of this launch
+            auto start = [&](V &v, uint32_t, const VoiceEv &ev, uint32_t r) {
+                const float *t = a.tp.vrec;
+                const uint32_t T = a.tp.n_v;
+                if (r != kNoCoef) {
+                    crec = r;
+                    amp_amt = t[VCC_AMP_AMT * T + r], port_c = t[VCC_PORT_COEF * T + r];
+                    inv_sr = t[VCC_INV_SR * T + r];
+                    cutoff = t[VCC_CUTOFF * T + r], fenv_amt = t[VCC_FENV_AMT * T + r];
+                    drive = t[VCC_DRIVE * T + r], fc_max = t[VCC_FC_MAX * T + r];
+                    K = t[VCC_LADDER_K * T + r];
+                    if constexpr (SVF)
+                        kc = SvfVoiceCoef{0.5f * amp_amt, port_c, inv_sr, cutoff, fenv_amt, fc_max, drive, K,
+                                          1.0f / (t[VCC_SR * T + r] * 2.0f)};
+                }
+                const bool rec = crec != kNoCoef;
+                voice_envs_restart(v, ev, rec ? t : c, rec ? T : n, rec ? crec : i);
+                if (ev.op & VEV_FREQ) {
+                    v.freq = ev.freq;
+                    v.set_freq = true;
+                }
+            };
+            sy::role_v<V, true, true>(b, load, run, store, &a, start, &a.tp);
         } else {
             sy::role_v<V>(b, load, run, store);
         }
@@ -171,15 +205,20 @@ __global__ __launch_bounds__(sy::kThreads) void synth_block(SynthArgs a) {
             }
         });
     } else {
-        sy::role_f<SVF>(b, a);
+        sy::role_f<SVF, TP>(b, a, [&]() -> const InstrumentTimed * {
+            if constexpr (TP) return &a.tp;
+            else return nullptr;
+        }());
     }
 }
 
-hipError_t launch_synth(const SynthArgs &a, hipStream_t s) {
+hipError_t launch_synth(const SynthSegArgs &a, hipStream_t s) {
     if (a.n == 0 || a.n_frames == 0) return hipSuccess;
-    if (!instrument_args_ok(a, kSyMaxVoices)) return hipErrorInvalidValue;
-    if (a.n_seg > 1u) return sy::launch(a.svf ? synth_block<true, true> : synth_block<false, true>, a, 0, s);
-    return sy::launch(a.svf ? synth_block<true, false> : synth_block<false, false>, a, 0, s);
+    if (!instrument_args_ok(a, kSyMaxVoices) || !instrument_timed_ok(a, a.tp, false)) return hipErrorInvalidValue;
+    if (a.tp.vtab) return sy::launch(a.svf ? synth_block<true, true, true> : synth_block<false, true, true>, a, 0, s);
+    const SynthArgs &plain = a;                            // (the other kernels take the arguments they always took)
+    if (a.n_seg > 1u) return sy::launch(a.svf ? synth_block<true, true> : synth_block<false, true>, plain, 0, s);
+    return sy::launch(a.svf ? synth_block<true, false> : synth_block<false, false>, plain, 0, s);
 }
 
 }  // namespace olfx

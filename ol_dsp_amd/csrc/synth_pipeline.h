@@ -110,18 +110,25 @@ __device__ __forceinline__ uint32_t d_instrument(const Wg &b) {
 // chunk of m frames ahead of the queue-V wait, its latency hidden under the previous chunk's consumers, handed on
 // in an X; run(v, x, q, m): the voice's samples of that chunk -> q[k * 64] (its column of queue V).
 //
-// SEG (timed notes, the *_seg kernels; a = the launch's arguments): only this role sees note events -- D and F are
-// continuous in time -- so the chunk grid, the queues, every counter and every wait stay as they are, and a V wave
-// splits a chunk's frames at the segment starts that fall inside it (multiples of 4: they can fall in mid-chunk).
+// SEG (timed notes, the *_seg kernels; a = the launch's arguments): only this role sees note events -- D is continuous
+// in time, and F but for its six coefficients (role_f, TP) -- so the chunk grid, the queues, every counter and every
+// wait stay as they are, and a V wave splits a chunk's frames at the segment starts that fall inside it (multiples of 4: they can fall in mid-chunk).
 // The pieces' samples go to the same queue-V columns, q[(k0 + k) * 64]; the wave waits once and publishes F_V
 // once per chunk, as without segments.  At a segment start, for va and vb in turn, start(v, p, ev) does from
 // registers what load does at a launch's start (voice_envs_restart and the voice's own events).  fetch runs per
 // piece -- the first piece's ahead of the wait, as ever -- so nothing fetched spans a segment start.  The next
 // segment's records and start frame are read one segment ahead (seg_event_fetch); the starts are clamped to the
 // block and forced to ascend, whatever the table holds, so a piece is 1 .. m frames inside its chunk.
-template <class V, class X, bool SEG = false, class Load, class Run, class Store, class Fetch, class Start = std::nullptr_t>
+// Timed parameters (tp; olfx_timed_instrument_params): a voice slot's table entry of the next segment is read one
+// segment ahead with its events (wave-uniform: scalar registers), and at the segment start start(v, p, ev, r) gets
+// the lane's voice record r (seg_inst_record; kNoCoef: none), which it takes ahead of the events -- parameters
+// precede notes.  TP is an instantiation of its own (the *_seg_tp kernels): a launch without such records runs the
+// SEG code as it was, start(v, p, ev) and all.
+template <class V, class X, bool SEG = false, bool TP = false, class Load, class Run, class Store, class Fetch,
+          class Start = std::nullptr_t>
 __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store, Fetch &&fetch,
-                                       const InstrumentArgs *a = nullptr, Start &&start = nullptr) {
+                                       const InstrumentArgs *a = nullptr, Start &&start = nullptr,
+                                       const InstrumentTimed *tp = nullptr) {
     const uint32_t wib = b.wib;
     if (wib >= b.nvw) return;
     const bool two = wib + (uint32_t)kVWaves < b.P;
@@ -133,11 +140,17 @@ __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Stor
     [[maybe_unused]] uint32_t sgi = 1u, S = 1u, nb = b.nf, gpa = 0u, gpb = 0u, groups = 0u, me = 0u;
     [[maybe_unused]] uint2 pa = make_uint2(0u, 0u), pb = make_uint2(0u, 0u);
     [[maybe_unused]] uint2 *slots = b.evslots + wib * 64u;
+    [[maybe_unused]] uint4 ta = make_uint4(0u, 0u, 0u, 0u), tb = ta;
+    [[maybe_unused]] uint32_t tga = 0u, tgb = 0u;
     [[maybe_unused]] auto ahead = [&] {
         if (sgi < S) {
             const uint32_t f = a->seg[sgi], lo = nb;       // (nb: the previous start)
             pa = seg_event_fetch(a->ev, sgi, groups, gpa, b.lane);
             if (two) pb = seg_event_fetch(a->ev, sgi, groups, gpb, b.lane);
+            if constexpr (TP) {
+                ta = tp->vtab[(size_t)sgi * tp->gv + tga];
+                tb = tp->vtab[(size_t)sgi * tp->gv + tgb];
+            }
             nb = min(max(f, lo), b.nf);
         } else {
             nb = b.nf;
@@ -149,6 +162,12 @@ __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Stor
         gpa = wib * (a->npad >> 6) + b.g;
         gpb = (wib + kVWaves) * (a->npad >> 6) + b.g;
         me = v_instrument(b) - b.g * 64u;
+        if constexpr (TP) {
+            // the table's group of each voice slot: the slot's own (a kit), or the instrument group (tp->gv = npad / 64)
+            const bool per_slot = tp->gv != (a->npad >> 6);
+            tga = per_slot ? gpa : b.g;
+            tgb = per_slot && two ? gpb : tga;
+        }
         nb = 0u;
         ahead();
     }
@@ -170,8 +189,15 @@ __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Stor
             bool waited = false;
             for (uint32_t k0 = 0; k0 < m;) {
                 while (sgi < S && nb == f0 + k0) {         // a segment starts at this frame
-                    start(va, wib, seg_event_take(pa, a->ev_more, slots, b.lane, me));
-                    if (two) start(vb, wib + kVWaves, seg_event_take(pb, a->ev_more, slots, b.lane, me));
+                    if constexpr (TP) {
+                        start(va, wib, seg_event_take(pa, a->ev_more, slots, b.lane, me), seg_inst_record(ta, me, tp->n_v));
+                        if (two)
+                            start(vb, wib + kVWaves, seg_event_take(pb, a->ev_more, slots, b.lane, me),
+                                  seg_inst_record(tb, me, tp->n_v));
+                    } else {
+                        start(va, wib, seg_event_take(pa, a->ev_more, slots, b.lane, me));
+                        if (two) start(vb, wib + kVWaves, seg_event_take(pb, a->ev_more, slots, b.lane, me));
+                    }
                     ++sgi;
                     ahead();
                 }
@@ -193,12 +219,12 @@ __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Stor
     if (two) store(vb, wib + kVWaves);
 }
 // a voice with nothing to fetch: run(v, q, m)
-template <class V, bool SEG = false, class Load, class Run, class Store, class Start = std::nullptr_t>
+template <class V, bool SEG = false, bool TP = false, class Load, class Run, class Store, class Start = std::nullptr_t>
 __device__ __forceinline__ void role_v(const Wg &b, Load &&load, Run &&run, Store &&store, const InstrumentArgs *a = nullptr,
-                                       Start &&start = nullptr) {
+                                       Start &&start = nullptr, const InstrumentTimed *tp = nullptr) {
     struct None {};
-    role_v<V, None, SEG>(
-        b, load, [&](V &v, None &, float *q, uint32_t m) { run(v, q, m); }, store, [](V &, uint32_t, None &) {}, a, start);
+    role_v<V, None, SEG, TP>(
+        b, load, [&](V &v, None &, float *q, uint32_t m) { run(v, q, m); }, store, [](V &, uint32_t, None &) {}, a, start, tp);
 }
 
 // ---------------- D: the delay stage, per (instrument, channel) lane ----------------
@@ -246,17 +272,37 @@ __device__ __forceinline__ void role_d(const Wg &b, const InstrumentArgs &a, Sum
 }
 
 // ---------------- F: the stub reverb's balance mix, filter_fx / filter1, the stores; lane = instrument ----------------
-template <bool TOPO>
-__device__ __forceinline__ void role_f(const Wg &b, const InstrumentArgs &a) {
+// TP (the *_seg_tp kernels; tp->ftab; olfx_timed_instrument_params): the six coefficients are loop-carried.  F reads
+// the segment table itself, one start and its table entry ahead; a chunk that holds a start (k = 0, 4, 8 or 12) runs
+// a second copy of the sample loop that, at each quad, lets the lanes with a rack record of a segment starting there
+// take it (seg_inst_record).  Every other chunk runs the loop it always ran; the waits and counters are unchanged.
+template <bool TOPO, bool TP = false>
+__device__ __forceinline__ void role_f(const Wg &b, const InstrumentArgs &a, const InstrumentTimed *tp = nullptr) {
     const uint32_t n = b.n, i_raw = b.g * 64u + b.lane;
     const bool valid = i_raw < n;
     const uint32_t i = valid ? i_raw : n - 1;
-    const float rbal = __uint_as_float(a.fr_coef[FRC_RBAL * n + i]);
-    const float ffreq = __uint_as_float(a.fr_coef[FRC_FFREQ * n + i]);
-    const float fdamp = __uint_as_float(a.fr_coef[FRC_FDAMP * n + i]);
-    const float fdrive = __uint_as_float(a.fr_coef[FRC_FDRIVE * n + i]);
-    const uint32_t ftype = a.fr_coef[FRC_FTYPE * n + i];
-    const float master = __uint_as_float(a.fr_coef[FRC_MASTER * n + i]);   // 1.0f: topology 1 (derive_fxrack)
+    float rbal = __uint_as_float(a.fr_coef[FRC_RBAL * n + i]);
+    float ffreq = __uint_as_float(a.fr_coef[FRC_FFREQ * n + i]);
+    float fdamp = __uint_as_float(a.fr_coef[FRC_FDAMP * n + i]);
+    float fdrive = __uint_as_float(a.fr_coef[FRC_FDRIVE * n + i]);
+    uint32_t ftype = a.fr_coef[FRC_FTYPE * n + i];
+    float master = __uint_as_float(a.fr_coef[FRC_MASTER * n + i]);   // 1.0f: topology 1 (derive_fxrack)
+    // TP: the segments F has yet to reach, the next one's start (clamped and ascending, as V's) and table entry
+    [[maybe_unused]] uint32_t fS = 1u, fsg = 1u, fnb = b.nf;
+    [[maybe_unused]] uint4 fe = make_uint4(0u, 0u, 0u, 0u);
+    [[maybe_unused]] const uint32_t fgroups = a.npad >> 6;
+    [[maybe_unused]] auto fahead = [&](uint32_t lo) {
+        if (fsg < fS) {
+            fnb = min(max(a.seg[fsg], lo), b.nf);
+            fe = tp->ftab[(size_t)fsg * fgroups + b.g];
+        } else {
+            fnb = b.nf;
+        }
+    };
+    if constexpr (TP) {
+        if (tp->n_f) fS = min(a.n_seg, kSegCap);
+        fahead(0u);
+    }
     // topology 0: FilterFx<2> writes channel 0 of the zeroed buf_c only, so out 1 = 0.0f x master
     bool fw = true;
     if constexpr (TOPO) fw = a.fr_coef[FRC_TOPO * n + i] == 1u;
@@ -272,6 +318,40 @@ __device__ __forceinline__ void role_f(const Wg &b, const InstrumentArgs &a) {
 #pragma unroll
         for (int k = 0; k < kChunk; ++k) a0[k] = q[k * 64];
         flag_put(b.flags + F_FIN, ck + 1);                 // (the release waits for these reads)
+        if constexpr (TP) {
+            if (fsg < fS && fnb < f0 + C) {                // wave-uniform: a segment starts inside this chunk
+#pragma unroll
+                for (int k = 0; k < kChunk; ++k) {
+                    if ((uint32_t)k < C) {
+                        if ((k & 3) == 0) {
+                            while (fsg < fS && fnb <= f0 + (uint32_t)k) {
+                                const uint32_t r = seg_inst_record(fe, i - b.g * 64u, tp->n_f);
+                                if (r != kNoCoef) {
+                                    const uint32_t *w = tp->frec + r;
+                                    const size_t T = tp->n_f;
+                                    rbal = __uint_as_float(w[TIF_RBAL * T]);
+                                    ffreq = __uint_as_float(w[TIF_FFREQ * T]);
+                                    fdamp = __uint_as_float(w[TIF_FDAMP * T]);
+                                    fdrive = __uint_as_float(w[TIF_FDRIVE * T]);
+                                    ftype = w[TIF_FTYPE * T];
+                                    master = __uint_as_float(w[TIF_MASTER * T]);
+                                }
+                                ++fsg;
+                                fahead(fnb);
+                            }
+                        }
+                        const float vb = a0[k] * 0.8f;
+                        const float b0 = (vb * rbal) + (a0[k] * (1 - rbal));
+                        const float c0 = fr::svf_tick(b0, ffreq, fdamp, fdrive, ftype, flow, fband);
+                        if (valid) {
+                            o0[(size_t)(f0 + k) * n] = c0 * master;
+                            o1[(size_t)(f0 + k) * n] = (fw ? b0 : 0.0f) * master;
+                        }
+                    }
+                }
+                continue;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < kChunk; ++k) {
             if ((uint32_t)k < C) {                         // C is wave-uniform

@@ -335,6 +335,17 @@ __device__ __forceinline__ VoiceEv seg_event_take(uint2 e, const uint2 *evs_more
     const uint2 v = slot[me];
     return VoiceEv{v.x, __uint_as_float(v.y)};
 }
+// Timed instrument parameters (InstrumentTimed): the record of lane `me` at a segment start from its group's table
+// entry, or kNoCoef.  No per-record index: the record is base + the lane's rank among the mask's lower bits.  Dead
+// lanes of the last group mirror instrument n - 1: `me` is that lane, so they take its bit and its rank.  A reload
+// is under the lane's own bit, and a number outside the section is no record, whatever the packet holds.
+__device__ __forceinline__ uint32_t seg_inst_record(uint4 e, uint32_t me, uint32_t count) {
+    const uint64_t mask = (uint64_t)e.x | (uint64_t)e.y << 32;
+    if (!mask) return kNoCoef;                             // wave-uniform: the common segment start
+    const bool has = (mask >> me) & 1ull;
+    const uint32_t r = e.z + (uint32_t)__builtin_popcountll(mask & ((1ull << me) - 1ull));
+    return has && r < count ? r : kNoCoef;
+}
 // A segment start from registers, what voice_envs_load does at a launch's start from the stored state: the flags
 // word from the live envelope modes, gprev and gate; the segment's gate events on it; both Env::begin.
 __device__ __forceinline__ void voice_envs_restart(VoiceEnvs &v, const VoiceEv &ev, const float *c, uint32_t cn, uint32_t ci) {

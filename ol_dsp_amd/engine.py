@@ -356,6 +356,50 @@ class Engine:
             arr[k].ev.source = _lib.CTL_HARDWARE if len(r) > 4 and r[4] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
         check(self.lib.olfx_timed_control(self._h, arr, len(recs)), self._h)
 
+    def timed_instrument_params(self, records) -> None:
+        """Parameter changes at a frame inside the coming blocks for the synth kinds and the drum kit
+        (olfx_timed_instrument_params): iterable of (frame, inst, field, value), or an array from
+        make_timed_params().  Each is set_param at its frame, ahead of that frame's notes; a write to a delay field
+        or the topology ends a launch there (the call runs as several launches)."""
+        if isinstance(records, np.ndarray):
+            if len(records):
+                check(self.lib.olfx_timed_instrument_params(self._h, records.ctypes.data_as(ctypes.POINTER(_lib.TimedParam)),
+                                                            len(records)), self._h)
+            return
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.TimedParam * len(recs))()
+        for k, r in enumerate(recs):
+            arr[k].frame = int(r[0])
+            arr[k].inst = int(r[1])
+            arr[k].field = self.field(r[2])
+            arr[k].value = float(r[3])
+        check(self.lib.olfx_timed_instrument_params(self._h, arr, len(recs)), self._h)
+
+    def timed_instrument_control(self, records) -> None:
+        """Control changes at a frame inside the coming blocks for the synth kinds and the drum kit
+        (olfx_timed_instrument_control): iterable of (frame, inst, cc, value[, source[, channel]]), or an array from
+        make_timed_control() (a kit: set its "pad" column to the channel).  Each is control() at its frame, mapped
+        there; a kit's channel is 0..15 or 16 for the rack."""
+        if isinstance(records, np.ndarray):
+            if len(records):
+                check(self.lib.olfx_timed_instrument_control(self._h, records.ctypes.data_as(ctypes.POINTER(_lib.TimedControl)),
+                                                             len(records)), self._h)
+            return
+        recs = list(records)
+        if not recs:
+            return
+        arr = (_lib.TimedControl * len(recs))()
+        for k, r in enumerate(recs):
+            arr[k].frame = int(r[0])
+            arr[k].ev.inst = int(r[1])
+            arr[k].ev.control = int(r[2])
+            arr[k].ev.value = float(r[3])
+            arr[k].ev.source = _lib.CTL_HARDWARE if len(r) > 4 and r[4] in ("hw", _lib.CTL_HARDWARE) else _lib.CTL_MIDI
+            arr[k].ev.pad = int(r[5]) if len(r) > 5 else 0
+        check(self.lib.olfx_timed_instrument_control(self._h, arr, len(recs)), self._h)
+
     def update(self, first: int = 0, count: int = -1) -> None:
         """Update() of instances first..first+count with their current parameters."""
         count = self.n - first if count < 0 else count
