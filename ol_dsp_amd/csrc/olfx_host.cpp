@@ -578,26 +578,25 @@ uint64_t state_bytes(int kind, uint32_t n, float sr) {
 
 void Shadow::derive_record(uint32_t i, uint32_t *w) const {
     // (an instrument whose last timed record still stands: the whole record, fold_segments derived it)
-    if (!ic_words.empty() && ic_of[i] >= 0) {
-        std::memcpy(w, ic_words.data() + ic_of[i], (size_t)kd->words * 4);
+    if (const uint32_t *kept = kept_inst.find(i)) {
+        std::memcpy(w, kept, (size_t)kd->words * 4);
         return;
     }
     float p[kMaxParams];
     for (uint32_t f = 0; f < n_params; ++f) p[f] = params[(size_t)f * n + i];
+    // (a voice whose last timed record still stands: those words, fold_segments derived them)
+    const uint32_t *const kept = kept_voice.find(i);
     for (uint32_t j = 0; j < kd->nparts; ++j) {
         const Component &c = kComponents[kd->parts[j].comp];
-        // (a voice whose last timed record still stands: those words, fold_segments derived them)
-        if (!tc_cache.empty() && kd->parts[j].comp == CP_VOICE && tc_cache_of[i] >= 0)
-            std::memcpy(w, tc_cache.data() + tc_cache_of[i], (size_t)VCC_N * 4);
-        else
-            c.derive(p + kd->parts[j].field0, *this, i, w);
+        if (kept && kd->parts[j].comp == CP_VOICE) std::memcpy(w, kept, (size_t)VCC_N * 4);
+        else c.derive(p + kd->parts[j].field0, *this, i, w);
         w += c.words;
     }
 }
 
 void Shadow::derive_voice_record(uint32_t hv, uint32_t *w) const {
-    if (!vc_words.empty() && vc_of[hv] >= 0) {           // (as derive_record: the slot's last timed record stands)
-        std::memcpy(w, vc_words.data() + vc_of[hv], (size_t)kd->vwords * 4);
+    if (const uint32_t *kept = kept_slot.find(hv)) {      // (as derive_record: the slot's last timed record stands)
+        std::memcpy(w, kept, (size_t)kd->vwords * 4);
         return;
     }
     const uint32_t p = hv / n, i = hv % n;
@@ -639,35 +638,28 @@ void Shadow::reset() {
         for (uint32_t f = 0; f < n_params; ++f)
             std::fill(params.begin() + (size_t)f * n, params.begin() + (size_t)(f + 1) * n, d[f]);
     }
-    configured.assign(kit() ? (size_t)voices * n : n, 0);
+    const size_t slots = kit() ? (size_t)voices * n : 0u;
+    configured.assign(kit() ? slots : n, 0);
+    kept_voice.init(kd->instances == KindDesc::VOICES ? n : 0u, VCC_N);
+    kept_inst.init(instruments() ? n : 0u, kd->words);
+    kept_slot.init(slots, kd->vwords);
     vdirty_list.clear();
-    vdirty_mark.assign(kit() ? (size_t)voices * n : 0u, 0);
-    for (uint32_t hv = 0; hv < vdirty_mark.size(); ++hv) mark_vdirty(hv);
+    vdirty_mark.assign(slots, 0);
+    for (uint32_t hv = 0; hv < slots; ++hv) mark_vdirty(hv);
     n_components = 0;
     pre_changed = true;
     events.clear();
     timed.clear();
     tparams.clear();
-    tc_inst.clear();
-    pre_valid = false;
-    tc_fresh = false;
-    tc_cache_of.assign(kd->instances == KindDesc::VOICES ? n : 0u, -1);
-    tc_cache.clear();
-    tc_cached.clear();
     iparams.clear();
-    ti_vlane.clear();
-    ti_flane.clear();
-    ti_inst.clear();
-    ti_slot.clear();
-    ti_fresh = false;
-    ti_vlast.assign(kit() ? (size_t)voices * n : instruments() ? n : 0u, -1);
-    ti_flast.assign(instruments() ? n : 0u, -1);
-    ic_of.assign(instruments() ? n : 0u, -1);
-    vc_of.assign(kit() ? (size_t)voices * n : 0u, -1);
-    ic_words.clear();
-    ic_list.clear();
-    vc_words.clear();
-    vc_list.clear();
+    vrec.clear();
+    frec.clear();
+    pre_valid = false;
+    fold_fresh = false;
+    changed_inst.clear();
+    changed_slot.clear();
+    last_v.assign(kit() ? slots : instruments() ? n : 0u, -1);
+    last_f.assign(instruments() ? n : 0u, -1);
     ev_slot.assign(n_ev(), -1);
     playing.assign((size_t)voices * n, 0);
     dirty_list.clear();
@@ -679,19 +671,18 @@ void Shadow::reset() {
 }
 
 void Shadow::mark_dirty(uint32_t first, uint32_t count) {
-    if (!tc_cache.empty())                                // whatever is written now, a kept timed record is stale
-        for (uint32_t k = first; k < first + count; ++k) tc_cache_of[k] = -1;
-    if (!ic_words.empty())
-        for (uint32_t k = first; k < first + count; ++k) ic_of[k] = -1;
-    for (uint32_t k = first; k < first + count; ++k)
+    for (uint32_t k = first; k < first + count; ++k) {
+        kept_voice.forget(k);                             // whatever is written now, a kept timed record is stale
+        kept_inst.forget(k);
         if (!dirty_mark[k]) {
             dirty_mark[k] = 1;
             dirty_list.push_back(k);
         }
+    }
 }
 
 void Shadow::mark_vdirty(uint32_t hv) {
-    if (!vc_words.empty()) vc_of[hv] = -1;
+    kept_slot.forget(hv);
     if (!vdirty_mark[hv]) {
         vdirty_mark[hv] = 1;
         vdirty_list.push_back(hv);
@@ -1114,6 +1105,67 @@ int Shadow::voice_events(const olfx_voice_event *ev, uint32_t count) {
     return OLFX_OK;
 }
 
+// ---- the timed calls: one discipline for the three pending lists (olfx_host.h) ----
+int Shadow::bad_frame(const char *call, const char *what, uint32_t k, uint32_t frame) {
+    if (!(frame & 3u) && frame < 0x80000000u) return OLFX_OK;
+    return fail(OLFX_E_ARG, "%s: %s %u: frame %u (a multiple of 4 below 2^31)", call, what, k, frame);
+}
+
+namespace {
+
+// `count` validated entries, entry(k) the k-th: one at frame 0 happens now (the untimed path: one order of arrival
+// for both), the rest go onto the pending list, stably by frame and behind the queued ones of their frame -- both
+// steps keep call order among ties
+template <class T, class Entry, class Now>
+void queue_by_frame(std::vector<T> &pending, size_t count, Entry &&entry, Now &&now) {
+    const size_t old = pending.size();
+    for (size_t k = 0; k < count; ++k) {
+        const T x = entry(k);
+        if (x.frame == 0u) now(x);
+        else pending.push_back(x);
+    }
+    const auto by_frame = [](const T &x, const T &y) { return x.frame < y.frame; };
+    std::stable_sort(pending.begin() + (ptrdiff_t)old, pending.end(), by_frame);
+    std::inplace_merge(pending.begin(), pending.begin() + (ptrdiff_t)old, pending.end(), by_frame);
+}
+
+// After a launch of `span` frames: the pending frames count from the next launch, and the entries that reached
+// frame 0 happen now, in order, and leave the list (`now` queues nothing onto it)
+template <class T, class Now>
+void shift_and_pop(std::vector<T> &pending, uint32_t span, Now &&now) {
+    for (T &x : pending) x.frame = x.frame > span ? x.frame - span : 0u;
+    size_t due = 0;
+    for (; due < pending.size() && !pending[due].frame; ++due) now(pending[due]);
+    pending.erase(pending.begin(), pending.begin() + (ptrdiff_t)due);
+}
+
+// The ascending union of the event times and the record times below `limit` (all past frame 0): per time,
+// f(t, e0, e1, r0, r1) with that time's events [e0, e1) and records [r0, r1); f returns false to stop ahead of that
+// time.  Returns the time it stopped at, or `limit`.
+template <class R, class F>
+uint32_t walk_times(const std::vector<olfx_timed_event> &ev, const std::vector<R> &rec, uint32_t limit, F &&f) {
+    const uint32_t none = 0xFFFFFFFFu;
+    for (size_t e = 0, r = 0;;) {
+        const uint32_t te = e < ev.size() ? ev[e].frame : none, tr = r < rec.size() ? rec[r].frame : none;
+        const uint32_t t = te < tr ? te : tr;
+        if (t >= limit) return limit;
+        size_t e1 = e, r1 = r;
+        while (e1 < ev.size() && ev[e1].frame == t) ++e1;
+        while (r1 < rec.size() && rec[r1].frame == t) ++r1;
+        if (!f(t, e, e1, r, r1)) return t;
+        e = e1;
+        r = r1;
+    }
+}
+
+// the lanes one time touches, each once and ascending (they mostly arrive that way)
+void sort_unique(std::vector<uint32_t> &v) {
+    if (!std::is_sorted(v.begin(), v.end())) std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+}
+
+}  // namespace
+
 int Shadow::timed_events(const olfx_timed_event *ev, uint32_t count) {
     if (!kd->takes_note_events()) return fail(OLFX_E_STATE, "olfx_timed_events: not a voice engine");
     // voice-addressed events; an instrument's notes are routed, at their frame: olfx_timed_notes
@@ -1121,27 +1173,13 @@ int Shadow::timed_events(const olfx_timed_event *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_timed_events: null events");
     for (uint32_t k = 0; k < count; ++k) {
         const olfx_voice_event &v = ev[k].ev;
-        if ((ev[k].frame & 3u) || ev[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_events: event %u: frame %u (a multiple of 4 below 2^31)", k, ev[k].frame);
+        if (const int rc = bad_frame("olfx_timed_events", "event", k, ev[k].frame)) return rc;
         if (v.inst >= n || v.note > 127 || v.type > OLFX_EV_SET_FREQUENCY ||
             (v.type == OLFX_EV_SET_FREQUENCY && !std::isfinite(v.value)))
             return fail(OLFX_E_ARG, "olfx_timed_events: bad event %u", k);
     }
-    // frame 0 is the untimed queue (one order of arrival for both calls); the rest merge into the pending
-    // list behind the queued events of their frame: both steps keep call order among ties
-    const size_t old = timed.size();
-    for (uint32_t k = 0; k < count; ++k) {
-        if (ev[k].frame == 0u) events.push_back(ev[k].ev);
-        else timed.push_back(ev[k]);
-    }
-    merge_timed(old);
+    queue_by_frame(timed, count, [&](size_t k) { return ev[k]; }, [&](const olfx_timed_event &t) { events.push_back(t.ev); });
     return OLFX_OK;
-}
-
-void Shadow::merge_timed(size_t old) {
-    const auto by_frame = [](const olfx_timed_event &x, const olfx_timed_event &y) { return x.frame < y.frame; };
-    std::stable_sort(timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
-    std::inplace_merge(timed.begin(), timed.begin() + (ptrdiff_t)old, timed.end(), by_frame);
 }
 
 // Timed notes of the synths and the drum kit.  A note is routed when the engine reaches its frame: a note at
@@ -1152,19 +1190,17 @@ int Shadow::timed_notes(const olfx_timed_note *ev, uint32_t count) {
     if (count && !ev) return fail(OLFX_E_ARG, "olfx_timed_notes: null events");
     for (uint32_t k = 0; k < count; ++k) {
         const olfx_event &v = ev[k].ev;
-        if ((ev[k].frame & 3u) || ev[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_notes: event %u: frame %u (a multiple of 4 below 2^31)", k, ev[k].frame);
+        if (const int rc = bad_frame("olfx_timed_notes", "event", k, ev[k].frame)) return rc;
         if (v.inst >= n || v.note > 127 || v.type > OLFX_EV_GATE_OFF) return fail(OLFX_E_ARG, "olfx_timed_notes: bad event %u", k);
         if (kit() && v.type > OLFX_EV_NOTE_ON)
             return fail(OLFX_E_ARG, "olfx_timed_notes: event %u: a drum kit takes NOTE_ON and NOTE_OFF only", k);
     }
-    const size_t old = timed.size();
-    for (uint32_t k = 0; k < count; ++k) {
-        const olfx_voice_event v{ev[k].ev.inst, ev[k].ev.type, ev[k].ev.note, ev[k].ev.velocity, 0, 0.f};
-        if (ev[k].frame == 0u) route_note(events, v);
-        else timed.push_back(olfx_timed_event{ev[k].frame, v});
-    }
-    merge_timed(old);
+    queue_by_frame(
+        timed, count,
+        [&](size_t k) {
+            return olfx_timed_event{ev[k].frame, olfx_voice_event{ev[k].ev.inst, ev[k].ev.type, ev[k].ev.note, ev[k].ev.velocity, 0, 0.f}};
+        },
+        [&](const olfx_timed_event &t) { route_note(events, t.ev); });
     return OLFX_OK;
 }
 
@@ -1177,14 +1213,7 @@ void Shadow::apply_param(const olfx_timed_param &r, bool mark) {
 }
 
 int Shadow::queue_params(const olfx_timed_param *rec, size_t count) {
-    const size_t old = tparams.size();
-    for (size_t k = 0; k < count; ++k) {
-        if (rec[k].frame == 0u) apply_param(rec[k], true);
-        else tparams.push_back(rec[k]);
-    }
-    const auto by_frame = [](const olfx_timed_param &x, const olfx_timed_param &y) { return x.frame < y.frame; };
-    std::stable_sort(tparams.begin() + (ptrdiff_t)old, tparams.end(), by_frame);
-    std::inplace_merge(tparams.begin(), tparams.begin() + (ptrdiff_t)old, tparams.end(), by_frame);
+    queue_by_frame(tparams, count, [&](size_t k) { return rec[k]; }, [&](const olfx_timed_param &r) { apply_param(r, true); });
     return OLFX_OK;
 }
 
@@ -1192,8 +1221,7 @@ int Shadow::timed_params(const olfx_timed_param *rec, uint32_t count) {
     if (kd->instances != KindDesc::VOICES) return fail(OLFX_E_KIND, "olfx_timed_params: the three voice kinds only");
     if (count && !rec) return fail(OLFX_E_ARG, "olfx_timed_params: null records");
     for (uint32_t k = 0; k < count; ++k) {
-        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_params: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (const int rc = bad_frame("olfx_timed_params", "record", k, rec[k].frame)) return rc;
         if (rec[k].inst >= n || rec[k].field >= n_params) return fail(OLFX_E_ARG, "olfx_timed_params: record %u out of range", k);
         if (const char *why = bad_value(rec[k].field, rec[k].value)) return fail(OLFX_E_ARG, "olfx_timed_params: record %u: %s", k, why);
     }
@@ -1208,8 +1236,7 @@ int Shadow::timed_control(const struct olfx_timed_control *rec, uint32_t count) 
     mapped.reserve(count);
     for (uint32_t k = 0; k < count; ++k) {
         const olfx_control_event &ev = rec[k].ev;
-        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_control: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (const int rc = bad_frame("olfx_timed_control", "record", k, rec[k].frame)) return rc;
         if (ev.inst >= n) return fail(OLFX_E_ARG, "olfx_timed_control: record %u: instance out of range", k);
         uint32_t fields[2];
         float vals[2];
@@ -1242,14 +1269,7 @@ void Shadow::apply_inst_now(const TimedInst &r) {
 }
 
 void Shadow::queue_inst(const std::vector<TimedInst> &recs) {
-    const size_t old = iparams.size();
-    for (const TimedInst &r : recs) {
-        if (r.frame == 0u) apply_inst_now(r);
-        else iparams.push_back(r);
-    }
-    const auto by_frame = [](const TimedInst &x, const TimedInst &y) { return x.frame < y.frame; };
-    std::stable_sort(iparams.begin() + (ptrdiff_t)old, iparams.end(), by_frame);
-    std::inplace_merge(iparams.begin(), iparams.begin() + (ptrdiff_t)old, iparams.end(), by_frame);
+    queue_by_frame(iparams, recs.size(), [&](size_t k) { return recs[k]; }, [&](const TimedInst &r) { apply_inst_now(r); });
 }
 
 int Shadow::timed_instrument_params(const olfx_timed_param *rec, uint32_t count) {
@@ -1259,8 +1279,7 @@ int Shadow::timed_instrument_params(const olfx_timed_param *rec, uint32_t count)
     std::vector<TimedInst> recs;
     recs.reserve(count);
     for (uint32_t k = 0; k < count; ++k) {
-        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (const int rc = bad_frame("olfx_timed_instrument_params", "record", k, rec[k].frame)) return rc;
         if (rec[k].inst >= n || rec[k].field >= n_params) return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u out of range", k);
         if (const char *why = bad_value(rec[k].field, rec[k].value))
             return fail(OLFX_E_ARG, "olfx_timed_instrument_params: record %u: %s", k, why);
@@ -1278,8 +1297,7 @@ int Shadow::timed_instrument_control(const struct olfx_timed_control *rec, uint3
     recs.reserve(count);
     for (uint32_t k = 0; k < count; ++k) {
         const olfx_control_event &ev = rec[k].ev;
-        if ((rec[k].frame & 3u) || rec[k].frame >= 0x80000000u)
-            return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: frame %u (a multiple of 4 below 2^31)", k, rec[k].frame);
+        if (const int rc = bad_frame("olfx_timed_instrument_control", "record", k, rec[k].frame)) return rc;
         if (ev.inst >= n) return fail(OLFX_E_ARG, "olfx_timed_instrument_control: record %u: instance out of range", k);
         // the mapping waits for the frame, so the record is judged under every mapping it can get there: a record
         // that olfx_control would refuse under one of them is refused now
@@ -1309,31 +1327,37 @@ int Shadow::timed_instrument_control(const struct olfx_timed_control *rec, uint3
 }
 
 // olfx_set_param's bookkeeping (store_param, touched) with logs in place of the dirty lists
-void Shadow::write_quiet(uint32_t inst, uint32_t field, float v, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f) {
+void Shadow::write_quiet(uint32_t inst, uint32_t field, float v) {
     store_param(field, inst, v);
     if (field >= kd->voice0 && field < kd->voice_end) {
         if (!kit()) {                                     // UpdateConfig + Update() of every voice of the instrument
             configured[inst] = 1;
             at_v.push_back(inst);
-            ti_inst.push_back(inst);
+            changed_inst.push_back(inst);
             return;
         }
         const uint32_t p = (field - kd->voice0) / OLFX_VC_NPARAMS;
         if (p < voices) {                                 // (a slot past the kit's voices is read by nothing)
             configured[(size_t)p * n + inst] = 1;
             at_v.push_back(p * n + inst);
-            ti_slot.push_back(p * n + inst);
+            changed_slot.push_back(p * n + inst);
         }
         return;
     }
     at_f.push_back(inst);
-    ti_inst.push_back(inst);
+    changed_inst.push_back(inst);
+}
+
+// a voice kind's record: olfx_set_param of that voice, which implies Update()
+void Shadow::apply_quiet(const olfx_timed_param &r) {
+    apply_param(r, false);
+    at_v.push_back(r.inst);
 }
 
 // Shadow::control's fan-out for one event, likewise
-void Shadow::apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f) {
+void Shadow::apply_quiet(const TimedInst &r) {
     if (!r.ctl) {
-        write_quiet(r.p.inst, r.p.field, r.p.value, at_v, at_f);
+        write_quiet(r.p.inst, r.p.field, r.p.value);
         return;
     }
     const olfx_control_event &ev = r.ev;
@@ -1346,9 +1370,9 @@ void Shadow::apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, s
         if (f == OLFX_FIELD_UPDATE_ONLY) {
             configured[(size_t)p * n + ev.inst] = 1;
             at_v.push_back(p * n + ev.inst);
-            ti_slot.push_back(p * n + ev.inst);
+            changed_slot.push_back(p * n + ev.inst);
         } else {
-            write_quiet(ev.inst, kd->voice0 + p * OLFX_VC_NPARAMS + f, v, at_v, at_f);
+            write_quiet(ev.inst, kd->voice0 + p * OLFX_VC_NPARAMS + f, v);
         }
         return;
     }
@@ -1362,9 +1386,9 @@ void Shadow::apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, s
                 configured[ev.inst] = 1;
                 at_v.push_back(ev.inst);
             }
-            ti_inst.push_back(ev.inst);
+            changed_inst.push_back(ev.inst);
         } else {
-            write_quiet(ev.inst, fields[h], vals[h], at_v, at_f);
+            write_quiet(ev.inst, fields[h], vals[h]);
         }
     }
 }
@@ -1375,100 +1399,66 @@ uint32_t timed_instrument_cap(int kind, uint32_t n, uint32_t voices) {
     return kd.voice_slots ? voices * n : n;
 }
 
-uint32_t Shadow::span(uint32_t n_frames) const {
-    uint32_t segs = 1, last = 0;                          // segment 0 starts at frame 0, events or none
-    if (has_timed_inst(n_frames)) {
-        // note times and record times in one ascending walk (all are past frame 0)
-        const uint32_t none = 0xFFFFFFFFu;
-        const size_t cap = timed_instrument_cap(kind, n, voices);
-        size_t ke = 0, kp = 0, recs = 0;
-        for (;;) {
-            const uint32_t te = ke < timed.size() ? timed[ke].frame : none, tp = kp < iparams.size() ? iparams[kp].frame : none;
-            const uint32_t t = te < tp ? te : tp;
-            if (t >= n_frames) return n_frames;
-            if (segs == kSegCap) return t;
-            if (tp == t) {
-                size_t c = 0;
-                for (; kp < iparams.size() && iparams[kp].frame == t; ++kp, ++c)
-                    if (is_boundary(iparams[kp])) return t;   // the next launch starts here, with it at frame 0
-                c = c < cap ? c : cap;                    // (a time changes at most `cap` lanes, however many records)
-                if (recs + c > cap) return t;             // (never a launch's first time: c <= cap)
-                recs += c;
-            }
-            while (ke < timed.size() && timed[ke].frame == t) ++ke;
-            ++segs;
-        }
-    }
-    if (!has_timed_params(n_frames)) {
-        for (const olfx_timed_event &t : timed) {
-            if (t.frame >= n_frames) break;
-            if (t.frame != last) {
-                if (segs == kSegCap) return t.frame;
-                ++segs;
-                last = t.frame;
-            }
-        }
-        return n_frames;
-    }
-    // event times and parameter times in one ascending walk (all are past frame 0); a parameter time adds a
-    // coefficient record per voice it changes, and the launch holds n of them
-    const uint32_t none = 0xFFFFFFFFu;
-    size_t ke = 0, kp = 0, recs = 0;
-    // (n records or fewer below the block: the record bound cannot bite, whatever voices they name)
-    size_t below = 0;
-    while (below < tparams.size() && tparams[below].frame < n_frames) ++below;
-    const bool count_voices = below > n;
-    std::vector<uint32_t> at;
-    for (;;) {
-        const uint32_t te = ke < timed.size() ? timed[ke].frame : none, tp = kp < tparams.size() ? tparams[kp].frame : none;
-        const uint32_t t = te < tp ? te : tp;
-        if (t >= n_frames) return n_frames;
-        if (segs == kSegCap) return t;
-        if (tp == t && !count_voices) {
-            while (kp < tparams.size() && tparams[kp].frame == t) ++kp;
-        } else if (tp == t) {
-            at.clear();
-            for (; kp < tparams.size() && tparams[kp].frame == t; ++kp) at.push_back(tparams[kp].inst);
-            std::sort(at.begin(), at.end());
-            const size_t c = (size_t)(std::unique(at.begin(), at.end()) - at.begin());
-            if (recs + c > n) return t;                   // (never the first time: c <= n)
+namespace {
+constexpr size_t kEndsLaunch = ~(size_t)0;
+
+// span() over the pending events and the kind's pending records: segment 0 starts at frame 0, events or none, and
+// every later time takes a segment.  adds(r0, r1): the coefficient records that a time's records [r0, r1) add to
+// the launch, of which it holds `cap`, or kEndsLaunch.
+template <class R, class Adds>
+uint32_t span_over(const std::vector<olfx_timed_event> &ev, const std::vector<R> &rec, uint32_t n_frames, size_t cap, Adds &&adds) {
+    uint32_t segs = 1;
+    size_t recs = 0;
+    return walk_times(ev, rec, n_frames, [&](uint32_t, size_t, size_t, size_t r0, size_t r1) {
+        if (segs == kSegCap) return false;
+        if (r1 > r0) {
+            const size_t c = adds(r0, r1);
+            if (c == kEndsLaunch || recs + c > cap) return false;      // (never a launch's first time: c <= cap)
             recs += c;
         }
-        while (ke < timed.size() && timed[ke].frame == t) ++ke;
         ++segs;
+        return true;
+    });
+}
+}  // namespace
+
+uint32_t Shadow::span(uint32_t n_frames) const {
+    const bool notes = !timed.empty() && timed.front().frame < n_frames;
+    if (!notes && !has_timed_params(n_frames) && !has_timed_inst(n_frames)) return n_frames;      // nothing past frame 0
+    if (instruments()) {
+        // a time's raw records, at most the cap (a time changes at most `cap` lanes, however many records); a
+        // boundary record ends the launch ahead of its time: the next one starts there, with it at frame 0
+        const size_t cap = timed_instrument_cap(kind, n, voices);
+        return span_over(timed, iparams, n_frames, cap, [&](size_t r0, size_t r1) {
+            for (size_t r = r0; r < r1; ++r)
+                if (is_boundary(iparams[r])) return kEndsLaunch;
+            return std::min(r1 - r0, cap);
+        });
     }
+    // a voice kind: a time adds a record per voice it changes (n records or fewer below the block: the bound cannot
+    // bite, whatever voices they name)
+    size_t below = 0;
+    while (below <= n && below < tparams.size() && tparams[below].frame < n_frames) ++below;
+    const bool count_voices = below > n;
+    std::vector<uint32_t> at;
+    return span_over(timed, tparams, n_frames, n, [&](size_t r0, size_t r1) {
+        if (!count_voices) return (size_t)0;
+        at.clear();
+        for (size_t r = r0; r < r1; ++r) at.push_back(tparams[r].inst);
+        sort_unique(at);
+        return at.size();
+    });
 }
 
 void Shadow::advance(uint32_t span_) {
-    // parameter records first: at a frame they precede the events, and one that reaches frame 0 lands now,
-    // ahead of anything set from now on
-    size_t q = 0;
-    for (olfx_timed_param &r : tparams) {
-        r.frame = r.frame > span_ ? r.frame - span_ : 0u;
-        if (!r.frame) {
-            apply_param(r, true);
-            ++q;
-        }
-    }
-    tparams.erase(tparams.begin(), tparams.begin() + (ptrdiff_t)q);
-    if (!iparams.empty()) {                               // (applying one can queue nothing: index, not iterate)
-        size_t qi = 0;
-        for (TimedInst &r : iparams) r.frame = r.frame > span_ ? r.frame - span_ : 0u;
-        while (qi < iparams.size() && !iparams[qi].frame) ++qi;
-        const std::vector<TimedInst> due(iparams.begin(), iparams.begin() + (ptrdiff_t)qi);
-        iparams.erase(iparams.begin(), iparams.begin() + (ptrdiff_t)qi);
-        for (const TimedInst &r : due) apply_inst_now(r);
-    }
-    size_t k = 0;
-    for (olfx_timed_event &t : timed) {
-        t.frame = t.frame > span_ ? t.frame - span_ : 0u;
-        if (!t.frame) {                                   // (ahead of anything queued from now on)
-            if (instruments()) route_note(events, t.ev);
-            else events.push_back(t.ev);
-            ++k;
-        }
-    }
-    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
+    // parameter records first: at a frame they precede the events, and one that reaches frame 0 lands now, ahead of
+    // anything set from now on; an instrument note that reaches frame 0 is routed now
+    shift_and_pop(tparams, span_, [&](const olfx_timed_param &r) { apply_param(r, true); });
+    shift_and_pop(iparams, span_, [&](const TimedInst &r) { apply_inst_now(r); });
+    shift_and_pop(timed, span_, [&](const olfx_timed_event &t) {
+        if (instruments()) route_note(events, t.ev);
+        else events.push_back(t.ev);
+    });
 }
 
 uint32_t Shadow::n_chunks(uint32_t span_, uint32_t chunk) const {
@@ -1614,175 +1604,102 @@ void Shadow::fold_events() {
 }
 
 // Timed events: every segment folds on its own, as the queue of a block that started at its frame would.
-// Timed parameters: a time's records are applied to the shadow here, in queueing order and ahead of that time's
-// events, and every voice they touch gets one coefficient record for the segment (derive_voice on the shadow as
-// that time leaves it) and VEV_COEF in its folded record.  The dirty instances' frame-0 records are derived
-// first (pre_words): fill_records runs after this fold and would see the later values.
-void Shadow::fold_segments(uint32_t span_) {
-    tc_inst.clear();
-    tc_words.clear();
-    tc_first.assign(1, 0u);
-    pre_valid = false;
-    tc_fresh = true;
-    ti_vlane.clear();
-    ti_flane.clear();
-    ti_fresh = false;
-    if (has_timed_inst(span_)) {
-        fold_instrument_segments(span_);
-        return;
-    }
-    if (has_timed_params(span_)) {
-        const size_t m = dirty_list.size(), W = kd->words;
+// Timed records (a voice kind's tparams, an instrument kind's iparams): a time's records are applied to the shadow
+// here, in queueing order -- an instrument's control mapped there -- and ahead of that time's events.  Every voice
+// (a synth: instrument; a kit: voice slot) whose voice fields they touch gets one voice record for the segment
+// (derive_voice on the shadow as that time leaves it), every instrument whose rack fields they touch one rack
+// record.  A voice kind's voice has VEV_COEF in its folded record; an instrument kind's tables say who has one.
+// The dirty records are derived first, as frame 0 has them: fill_records runs after this fold and would see the
+// later values.
+template <class R>
+void Shadow::fold_with(std::vector<R> &pending, uint32_t span_) {
+    const bool recs = !pending.empty() && pending.front().frame < span_;
+    vrec.clear();
+    frec.clear();
+    pre_valid = fold_fresh = recs;
+    if (recs) {
+        const size_t m = dirty_list.size(), W = kd->words, m2 = vdirty_list.size(), W2 = kd->vwords;
         pre_words.resize(m * W);
         for (size_t r = 0; r < m; ++r) derive_record(m == n ? (uint32_t)r : dirty_list[r], pre_words.data() + r * W);
-        pre_valid = true;
-        fold_events();                                    // segment 0: the frame-0 queue
-        tc_first.push_back(0u);
-        const uint32_t none = 0xFFFFFFFFu;
-        size_t k = 0, q = 0;
-        std::vector<uint32_t> at;
-        for (;;) {
-            const uint32_t te = k < timed.size() ? timed[k].frame : none, tp = q < tparams.size() ? tparams[q].frame : none;
-            const uint32_t t = te < tp ? te : tp;
-            if (t >= span_) break;
-            seg_frame.push_back(t);
-            at.clear();
-            for (; q < tparams.size() && tparams[q].frame == t; ++q) {
-                apply_param(tparams[q], false);
-                at.push_back(tparams[q].inst);
-            }
-            if (!std::is_sorted(at.begin(), at.end())) std::sort(at.begin(), at.end());
-            at.erase(std::unique(at.begin(), at.end()), at.end());
-            for (const uint32_t v : at) {
-                float p[OLFX_VC_NPARAMS];
-                for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) p[f] = params[(size_t)(kd->voice0 + f) * n + v];
-                tc_words.resize(tc_words.size() + VCC_N);
-                derive_voice(p, configured[v] != 0, kd->moog, sr, tc_words.data() + tc_words.size() - VCC_N);
-                tc_inst.push_back(v);
-            }
-            size_t k1 = k;
-            while (k1 < timed.size() && timed[k1].frame == t) ++k1;
-            fold_one(k1 > k ? &timed[k].ev : nullptr, k1 - k, sizeof(olfx_timed_event), at.data(), at.size());
-            seg_first.push_back((uint32_t)folded.size());
-            tc_first.push_back((uint32_t)tc_inst.size());
-            k = k1;
-        }
-        timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
-        tparams.erase(tparams.begin(), tparams.begin() + (ptrdiff_t)q);
-        return;
+        pre_vwords.resize(m2 * W2);
+        for (size_t r = 0; r < m2; ++r) derive_voice_record(vdirty_list[r], pre_vwords.data() + r * W2);
+        vrec.open();
+        frec.open();
+        rack_full.clear();
+        changed_inst.clear();
+        changed_slot.clear();
     }
     fold_events();                                        // segment 0: the frame-0 queue
-    size_t k = 0;
-    while (k < timed.size() && timed[k].frame < span_) {
-        size_t k1 = k;
-        while (k1 < timed.size() && timed[k1].frame == timed[k].frame) ++k1;
-        seg_frame.push_back(timed[k].frame);
-        if (instruments()) {                              // routed now, against Playing() as the frames before left it
-            routed.clear();
-            for (size_t j = k; j < k1; ++j) route_note(routed, timed[j].ev);
-            fold_one(routed.data(), routed.size(), sizeof(olfx_voice_event));
-        } else {
-            fold_one(&timed[k].ev, k1 - k, sizeof(olfx_timed_event));
-        }
-        seg_first.push_back((uint32_t)folded.size());
-        k = k1;
-    }
-    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
-}
-
-// The instrument kinds with timed records: a time's records are applied to the shadow in queueing order, a control
-// mapped there, ahead of routing that time's notes; every instrument (a kit: voice slot) whose voice fields they
-// touch gets one voice record for the segment, every instrument whose rack fields they touch one rack record.  The
-// dirty instances' frame-0 records are derived first (pre_words, pre_vwords), and what the records changed is
-// listed with its last record (ti_inst, ti_slot) for fill_records to put back on the dirty lists.
-void Shadow::fold_instrument_segments(uint32_t span_) {
-    const size_t m = dirty_list.size(), W = kd->words, m2 = vdirty_list.size(), W2 = kd->vwords;
-    pre_words.resize(m * W);
-    for (size_t r = 0; r < m; ++r) derive_record(m == n ? (uint32_t)r : dirty_list[r], pre_words.data() + r * W);
-    pre_vwords.resize(m2 * W2);
-    for (size_t r = 0; r < m2; ++r) derive_voice_record(vdirty_list[r], pre_vwords.data() + r * W2);
-    pre_valid = true;
-    // (the previous launch's kept records have served: what is derived from here on is derived afresh)
-    for (const uint32_t i : ic_list) ic_of[i] = -1;
-    for (const uint32_t hv : vc_list) vc_of[hv] = -1;
-    ic_words.clear();
-    ic_list.clear();
-    vc_words.clear();
-    vc_list.clear();
-    ti_inst.clear();
-    ti_slot.clear();
-    ti_vwords.clear();
-    ti_fwords.clear();
-    ti_ffull.clear();
-    fold_events();                                        // segment 0: the frame-0 queue
-    ti_vfirst.assign(2, 0u);
-    ti_ffirst.assign(2, 0u);
-    const uint32_t none = 0xFFFFFFFFu;
-    size_t k = 0, q = 0;
-    std::vector<uint32_t> at_v, at_f;
-    uint32_t fw[FRC_N];
-    float p[std::max<uint32_t>(OLFX_FR_NPARAMS, OLFX_VC_NPARAMS)];
-    auto uniq = [](std::vector<uint32_t> &v) {
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-    };
-    for (;;) {
-        const uint32_t te = k < timed.size() ? timed[k].frame : none, tp = q < iparams.size() ? iparams[q].frame : none;
-        const uint32_t t = te < tp ? te : tp;
-        if (t >= span_) break;
+    size_t n_ev_done = 0, n_rec_done = 0;
+    walk_times(timed, pending, span_, [&](uint32_t t, size_t e0, size_t e1, size_t r0, size_t r1) {
         seg_frame.push_back(t);
         at_v.clear();
         at_f.clear();
-        for (; q < iparams.size() && iparams[q].frame == t; ++q) apply_inst_quiet(iparams[q], at_v, at_f);
-        uniq(at_v);
-        uniq(at_f);
-        for (const uint32_t v : at_v) {                   // a synth: the instrument; a kit: hv = slot * n + kit
+        for (size_t r = r0; r < r1; ++r) apply_quiet(pending[r]);
+        sort_unique(at_v);
+        sort_unique(at_f);
+        float p[std::max<uint32_t>(OLFX_FR_NPARAMS, OLFX_VC_NPARAMS)];
+        for (const uint32_t v : at_v) {                   // a voice, a synth's instrument, a kit's hv = slot * n + kit
             const uint32_t slot = kit() ? v / n : 0u, i = kit() ? v % n : v;
             for (uint32_t f = 0; f < OLFX_VC_NPARAMS; ++f) p[f] = params[(size_t)(kd->voice0 + slot * OLFX_VC_NPARAMS + f) * n + i];
-            ti_vwords.resize(ti_vwords.size() + VCC_N);
-            derive_voice(p, configured[v] != 0, kd->moog, sr, ti_vwords.data() + ti_vwords.size() - VCC_N);
-            ti_vlast[v] = (int32_t)ti_vlane.size();
-            ti_vlane.push_back(kit() ? slot * npad + i : i);
+            if (instruments()) last_v[v] = (int32_t)vrec.size();
+            derive_voice(p, configured[v] != 0, kd->moog, sr, vrec.add(kit() ? slot * npad + i : i));
         }
-        const uint32_t rack0 = kd->topo_field - OLFX_FR_TOPOLOGY;
         for (const uint32_t i : at_f) {
+            const uint32_t rack0 = kd->topo_field - OLFX_FR_TOPOLOGY;
+            uint32_t fw[FRC_N];
             for (uint32_t f = 0; f < OLFX_FR_NPARAMS; ++f) p[f] = params[(size_t)(rack0 + f) * n + i];
             derive_fxrack(p, sr, fw);
-            ti_fwords.insert(ti_fwords.end(), fw + FRC_RBAL, fw + FRC_RBAL + TIF_N);
-            ti_ffull.insert(ti_ffull.end(), fw, fw + FRC_N);
-            ti_flast[i] = (int32_t)ti_flane.size();
-            ti_flane.push_back(i);
+            last_f[i] = (int32_t)frec.size();
+            std::memcpy(frec.add(i), fw + FRC_RBAL, (size_t)TIF_N * 4);
+            rack_full.insert(rack_full.end(), fw, fw + FRC_N);
         }
-        size_t k1 = k;
-        while (k1 < timed.size() && timed[k1].frame == t) ++k1;
-        routed.clear();                                   // parameters precede the notes of their frame
-        for (size_t j = k; j < k1; ++j) route_note(routed, timed[j].ev);
-        fold_one(routed.data(), routed.size(), sizeof(olfx_voice_event));
+        if (instruments()) {                              // routed now, against Playing() as the frames before left it
+            routed.clear();
+            for (size_t e = e0; e < e1; ++e) route_note(routed, timed[e].ev);
+            fold_one(routed.data(), routed.size(), sizeof(olfx_voice_event));
+        } else {
+            fold_one(e1 > e0 ? &timed[e0].ev : nullptr, e1 - e0, sizeof(olfx_timed_event), at_v.data(), at_v.size());
+        }
         seg_first.push_back((uint32_t)folded.size());
-        ti_vfirst.push_back((uint32_t)ti_vlane.size());
-        ti_ffirst.push_back((uint32_t)ti_flane.size());
-        k = k1;
-    }
-    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)k);
-    iparams.erase(iparams.begin(), iparams.begin() + (ptrdiff_t)q);
-    uniq(ti_inst);
-    uniq(ti_slot);
-    // the last records, whole: an instrument's (a slot's) latest voice record and latest rack record of this fold are
-    // its voice and rack words as the launch leaves them -- nothing is derived a second time; the parts no record of
-    // the fold covers are derived here
-    ti_inst_words.resize(ti_inst.size() * W);
+        if (recs) {
+            vrec.close_segment();
+            frec.close_segment();
+        }
+        n_ev_done = e1;
+        n_rec_done = r1;
+        return true;
+    });
+    timed.erase(timed.begin(), timed.begin() + (ptrdiff_t)n_ev_done);
+    pending.erase(pending.begin(), pending.begin() + (ptrdiff_t)n_rec_done);
+    if (recs && instruments()) keep_last_records();
+}
+
+void Shadow::fold_segments(uint32_t span_) {
+    if (instruments()) fold_with(iparams, span_);
+    else fold_with(tparams, span_);
+}
+
+// The whole last records of what an instrument fold changed: an instrument's (a slot's) latest voice record and
+// latest rack record of the fold are its voice and rack words as the launch leaves them -- nothing is derived a
+// second time; the parts no record of the fold covers are derived here.
+void Shadow::keep_last_records() {
+    const size_t W = kd->words, W2 = kd->vwords;
+    sort_unique(changed_inst);
+    sort_unique(changed_slot);
+    changed_inst_words.resize(changed_inst.size() * W);
     float all[kMaxParams];
-    for (size_t r = 0; r < ti_inst.size(); ++r) {
-        const uint32_t i = ti_inst[r];
-        uint32_t *w = ti_inst_words.data() + r * W;
+    for (size_t r = 0; r < changed_inst.size(); ++r) {
+        const uint32_t i = changed_inst[r];
+        uint32_t *w = changed_inst_words.data() + r * W;
         bool have = false;
         for (uint32_t j = 0; j < kd->nparts; ++j) {
             const Part &pt = kd->parts[j];
             const Component &c = kComponents[pt.comp];
-            if (pt.comp == CP_VOICE && ti_vlast[i] >= 0) {
-                std::memcpy(w, ti_vwords.data() + (size_t)ti_vlast[i] * VCC_N, (size_t)VCC_N * 4);
-            } else if (pt.comp == CP_RACK && ti_flast[i] >= 0) {
-                std::memcpy(w, ti_ffull.data() + (size_t)ti_flast[i] * FRC_N, (size_t)FRC_N * 4);
+            if (pt.comp == CP_VOICE && last_v[i] >= 0) {
+                std::memcpy(w, vrec.words.data() + (size_t)last_v[i] * VCC_N, (size_t)VCC_N * 4);
+            } else if (pt.comp == CP_RACK && last_f[i] >= 0) {
+                std::memcpy(w, rack_full.data() + (size_t)last_f[i] * FRC_N, (size_t)FRC_N * 4);
             } else {
                 if (!have)
                     for (uint32_t f = 0; f < n_params; ++f) all[f] = params[(size_t)f * n + i];
@@ -1792,17 +1709,15 @@ void Shadow::fold_instrument_segments(uint32_t span_) {
             w += c.words;
         }
     }
-    ti_slot_words.resize(ti_slot.size() * W2);
-    for (size_t r = 0; r < ti_slot.size(); ++r) {             // (a listed slot has a voice record in this fold)
-        const uint32_t hv = ti_slot[r];
-        uint32_t *w = ti_slot_words.data() + r * W2;
-        std::memcpy(w, ti_vwords.data() + (size_t)ti_vlast[hv] * VCC_N, (size_t)VCC_N * 4);
+    changed_slot_words.resize(changed_slot.size() * W2);
+    for (size_t r = 0; r < changed_slot.size(); ++r) {    // (a listed slot has a voice record in this fold)
+        const uint32_t hv = changed_slot[r];
+        uint32_t *w = changed_slot_words.data() + r * W2;
+        std::memcpy(w, vrec.words.data() + (size_t)last_v[hv] * VCC_N, (size_t)VCC_N * 4);
         sample_record(hv % n * voices + hv / n, w + VCC_N);
     }
-    for (const uint32_t i : ti_inst) ti_flast[i] = -1;
-    if (kit()) for (const uint32_t hv : ti_slot) ti_vlast[hv] = -1;
-    else for (const uint32_t i : ti_inst) ti_vlast[i] = -1;
-    ti_fresh = true;
+    for (const uint32_t i : changed_inst) last_f[i] = -1;
+    for (const uint32_t v : kit() ? changed_slot : changed_inst) last_v[v] = -1;
 }
 
 // `count` events `stride` bytes apart
@@ -1936,41 +1851,44 @@ size_t max_timed_instrument_words(int kind, uint32_t n, uint32_t voices) {
     return 3 + 4 * (size_t)kSegCap * (gv + g) + (size_t)VCC_N * cap + 3 + (size_t)TIF_N * cap;
 }
 
-void Shadow::write_timed_inst(const PacketPlan &pl, uint32_t *buf) const {
-    // a table: per segment and group, the lanes that have a record and the number of the first (ascending lanes:
-    // a group's run starts where the group before it ends)
-    auto table = [&](uint32_t *tab, size_t groups, const std::vector<uint32_t> &lane, const std::vector<uint32_t> &first) {
-        std::memset(tab, 0, 4 * pl.n_seg * groups * 4);
-        for (size_t s = 0; s + 1 < first.size() && s < pl.n_seg; ++s) {
-            size_t r = first[s];
-            for (size_t g = 0; g < groups; ++g) {
-                uint32_t *e = tab + 4 * (s * groups + g);
-                e[2] = (uint32_t)r;
-                for (; r < first[s + 1] && (lane[r] >> 6) == g; ++r) e[(lane[r] & 63u) >> 5] |= 1u << (lane[r] & 31u);
-            }
+namespace {
+// Per segment and 64-lane group of `rec`, in order: f(s, g, r0, r1), the group's run of records [r0, r1) (ascending
+// lanes: a group's run starts where the group before it ends)
+template <class Rec, class F>
+void for_group_runs(const Rec &rec, size_t groups, F &&f) {
+    for (size_t s = 0; s + 1 < rec.first.size(); ++s) {
+        size_t r = rec.first[s];
+        for (size_t g = 0; g < groups; ++g) {
+            const size_t r0 = r;
+            while (r < rec.first[s + 1] && (rec.lane[r] >> 6) == g) ++r;
+            f(s, g, r0, r);
         }
+    }
+}
+}  // namespace
+
+void Shadow::write_timed_inst(const PacketPlan &pl, uint32_t *buf) const {
+    // a table: per segment and group, the lanes that have a record and the number of the first
+    auto table = [&](uint32_t *tab, size_t groups, const auto &rec) {
+        std::memset(tab, 0, 4 * pl.n_seg * groups * 4);
+        for_group_runs(rec, groups, [&](size_t s, size_t g, size_t r0, size_t r1) {
+            uint32_t *e = tab + 4 * (s * groups + g);
+            e[2] = (uint32_t)r0;
+            for (size_t r = r0; r < r1; ++r) e[(rec.lane[r] & 63u) >> 5] |= 1u << (rec.lane[r] & 31u);
+        });
     };
-    table(buf + pl.o_ivt, pl.gv, ti_vlane, ti_vfirst);
-    table(buf + pl.o_ift, pl.gf, ti_flane, ti_ffirst);
-    for (size_t r = 0; r < pl.n_iv; ++r)
-        for (uint32_t w = 0; w < VCC_N; ++w) buf[pl.o_iv + (size_t)w * pl.n_iv + r] = ti_vwords[r * VCC_N + w];
+    table(buf + pl.o_ivt, pl.gv, vrec);
+    table(buf + pl.o_ift, pl.gf, frec);
+    vrec.write_field_major(buf + pl.o_iv);
     for (size_t w = pl.o_iv + (size_t)VCC_N * pl.n_iv; w < pl.o_if; ++w) buf[w] = 0u;
-    for (size_t r = 0; r < pl.n_if; ++r)
-        for (uint32_t w = 0; w < TIF_N; ++w) buf[pl.o_if + (size_t)w * pl.n_if + r] = ti_fwords[r * TIF_N + w];
+    frec.write_field_major(buf + pl.o_if);
 }
 
 void Shadow::write_timed_coefs(const PacketPlan &pl, uint32_t *buf) const {
-    const size_t groups = (n_ev() + 63u) / 64u, T = tc_inst.size();
-    uint32_t *base = buf + pl.o_tcb, *rec = buf + pl.o_tc;
-    for (size_t s = 0; s + 1 < tc_first.size(); ++s) {
-        size_t r = tc_first[s];                           // ascending voices: group g's run starts where g - 1's ends
-        for (size_t g = 0; g < groups; ++g) {
-            base[s * groups + g] = (uint32_t)r;
-            while (r < tc_first[s + 1] && (tc_inst[r] >> 6) == g) ++r;
-        }
-    }
-    for (size_t r = 0; r < T; ++r)
-        for (uint32_t w = 0; w < VCC_N; ++w) rec[(size_t)w * T + r] = tc_words[r * VCC_N + w];
+    const size_t groups = (n_ev() + 63u) / 64u;
+    uint32_t *base = buf + pl.o_tcb;
+    for_group_runs(vrec, groups, [&](size_t s, size_t g, size_t r0, size_t) { base[s * groups + g] = (uint32_t)r0; });
+    vrec.write_field_major(buf + pl.o_tc);
 }
 
 size_t max_packet_words(int kind, uint32_t n_inst, uint32_t n_ev, uint32_t n_seg) {
@@ -2000,15 +1918,16 @@ bool Shadow::ring_free_next() const {
 }
 
 void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
+    // the dirty instances' records, then a kit kind's dirty voice slots' (listed by device slot p * npad + kit):
+    // frame 0's where a fold derived them ahead of its records
     const size_t m = dirty_list.size();
-    const uint32_t W = kd->words;
-    uint32_t *val = buf + pl.o_val;
-    h_words.resize(W);
+    const uint32_t W = kd->words, W2 = kd->vwords;
+    h_words.resize(std::max(W, W2));
     bool pitch_changed = false;
     for (size_t r = 0; r < m; ++r) {
         const uint32_t i = pl.dense ? (uint32_t)r : dirty_list[r];
         if (!pl.dense) buf[pl.o_inst + r] = i;
-        if (pre_valid) std::memcpy(h_words.data(), pre_words.data() + r * W, (size_t)W * 4);   // frame 0's (fold_segments)
+        if (pre_valid) std::memcpy(h_words.data(), pre_words.data() + r * W, (size_t)W * 4);
         else derive_record(i, h_words.data());
         if (kind == OLFX_KIND_CHORUS)
             for (uint32_t k = 0; k < 4; ++k) {
@@ -2016,68 +1935,39 @@ void Shadow::fill_records(const PacketPlan &pl, uint32_t *buf) {
                 pitch_changed |= sent != h_words[kPitchWords[k]];
                 sent = h_words[kPitchWords[k]];
             }
-        for (uint32_t w = 0; w < W; ++w) val[(size_t)w * m + r] = h_words[w];
+        for (uint32_t w = 0; w < W; ++w) buf[pl.o_val + (size_t)w * m + r] = h_words[w];
     }
+    for (size_t r = 0; r < pl.m2; ++r) {
+        const uint32_t hv = vdirty_list[r];
+        buf[pl.o_inst2 + r] = hv / n * npad + hv % n;
+        if (pre_valid) std::memcpy(h_words.data(), pre_vwords.data() + r * W2, (size_t)W2 * 4);
+        else derive_voice_record(hv, h_words.data());
+        for (uint32_t w = 0; w < W2; ++w) buf[pl.o_val2 + (size_t)w * pl.m2 + r] = h_words[w];
+    }
+    pre_valid = false;
     for (const uint32_t i : dirty_list) dirty_mark[i] = 0;
     dirty_list.clear();
-    // the voices the launch's timed records change stay dirty: the device arrays get their last record ahead of
-    // the next launch (the kernels never write the coefficient arrays)
-    const bool had_pre = pre_valid && instruments();
-    pre_valid = false;
-    if (!tc_cache.empty()) {                              // the previous launch's voices alone: nothing else is set
-        for (const uint32_t i : tc_cached) tc_cache_of[i] = -1;
-        tc_cached.clear();
-        tc_cache.clear();
+    for (const uint32_t hv : vdirty_list) vdirty_mark[hv] = 0;
+    vdirty_list.clear();
+    // the previous launch's kept records have served (nothing to do where there are none)
+    kept_voice.forget_all();
+    kept_inst.forget_all();
+    kept_slot.forget_all();
+    // what the fold's records changed stays dirty, with its last record kept: the device arrays get it ahead of the
+    // next launch (the kernels never write the coefficient arrays).  Once per fold: a later packet without a fold of
+    // its own must not see this launch's records again
+    if (fold_fresh && instruments()) {
+        for (const uint32_t i : changed_inst) mark_dirty(i, 1);
+        for (const uint32_t hv : changed_slot) mark_vdirty(hv);
+        kept_inst.keep(changed_inst, changed_inst_words);
+        kept_slot.keep(changed_slot, changed_slot_words);
+        changed_inst.clear();
+        changed_slot.clear();
+    } else if (fold_fresh) {
+        for (const uint32_t v : vrec.lane) mark_dirty(v, 1);
+        kept_voice.keep(vrec.lane, vrec.words);
     }
-    // (once per fold: a later packet without a fold of its own must not see this launch's records again)
-    for (size_t r = 0; tc_fresh && r < tc_inst.size(); ++r) {     // in segment order: a voice's last record stays
-        mark_dirty(tc_inst[r], 1);
-        if (!tc_cache_of.empty()) tc_cache_of[tc_inst[r]] = (int32_t)(r * VCC_N);
-    }
-    if (tc_fresh && !tc_inst.empty() && !tc_cache_of.empty()) {
-        tc_cache = tc_words;
-        tc_cached = tc_inst;
-    }
-    tc_fresh = false;
-    // a kit kind's voice slots: listed by device slot p * npad + kit
-    if (pl.m2) {
-        const uint32_t W2 = kd->vwords;
-        h_words.resize(W2);
-        for (size_t r = 0; r < pl.m2; ++r) {
-            const uint32_t hv = vdirty_list[r];
-            buf[pl.o_inst2 + r] = hv / n * npad + hv % n;
-            if (had_pre) std::memcpy(h_words.data(), pre_vwords.data() + r * W2, (size_t)W2 * 4);   // frame 0's
-            else derive_voice_record(hv, h_words.data());
-            for (uint32_t w = 0; w < W2; ++w) buf[pl.o_val2 + (size_t)w * pl.m2 + r] = h_words[w];
-            vdirty_mark[hv] = 0;
-        }
-        vdirty_list.clear();
-    }
-    // timed instrument records: the previous launch's kept records have served; this launch's instruments and voice
-    // slots go back on the lists with their last record (once per fold, as above)
-    if (!ic_words.empty() || !vc_words.empty()) {
-        for (const uint32_t i : ic_list) ic_of[i] = -1;
-        for (const uint32_t hv : vc_list) vc_of[hv] = -1;
-        ic_words.clear();
-        ic_list.clear();
-        vc_words.clear();
-        vc_list.clear();
-    }
-    if (ti_fresh) {
-        for (size_t r = 0; r < ti_inst.size(); ++r) mark_dirty(ti_inst[r], 1);
-        for (size_t r = 0; r < ti_slot.size(); ++r) mark_vdirty(ti_slot[r]);
-        ic_words.swap(ti_inst_words);
-        ic_list.swap(ti_inst);
-        vc_words.swap(ti_slot_words);
-        vc_list.swap(ti_slot);
-        for (size_t r = 0; r < ic_list.size(); ++r) ic_of[ic_list[r]] = (int32_t)(r * W);
-        for (size_t r = 0; r < vc_list.size(); ++r) vc_of[vc_list[r]] = (int32_t)(r * kd->vwords);
-        ti_inst_words.clear();
-        ti_inst.clear();
-        ti_slot_words.clear();
-        ti_slot.clear();
-        ti_fresh = false;
-    }
+    fold_fresh = false;
     if (pitch_changed && rf.changed()) rf_materialise = true;
 }
 

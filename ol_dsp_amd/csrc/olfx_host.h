@@ -3,6 +3,9 @@
 // host shadow of an engine's parameters with its validation and bookkeeping, and the format of the
 // control packet.  olfx_engine.cpp owns a Shadow by value and delivers the packets it fills;
 // tests/cpp/test_host_core.cpp drives the same code on the CPU.
+// The timed calls share one path: three pending lists under one discipline (frame check, merge by frame, shift and
+// pop), one walk over the times of a launch for span() and fold_segments(), the launch's coefficient records in
+// SegRecords and the records kept for the next scatter in KeptRecords.  tests/cpp/dump_packets.cpp pins its packets.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -157,6 +160,50 @@ struct TimedInst {
     olfx_control_event ev;                // ctl
 };
 
+// A launch's timed coefficient records of W words each, segment by segment: segment s is records first[s] ..
+// first[s + 1], ascending by lane inside a segment; words [records][W].
+template <uint32_t W>
+struct SegRecords {
+    std::vector<uint32_t> lane, first, words;
+    void clear() { lane.clear(); first.clear(); words.clear(); }
+    void open() { clear(); first.assign(2, 0u); }                     // segment 0 (frame 0) has none
+    uint32_t *add(uint32_t lane_) {
+        lane.push_back(lane_);
+        words.resize(words.size() + W);
+        return words.data() + words.size() - W;
+    }
+    void close_segment() { first.push_back((uint32_t)lane.size()); }
+    size_t size() const { return lane.size(); }
+    void write_field_major(uint32_t *dst) const {                     // [W][records]
+        const size_t T = lane.size();
+        const uint32_t *src = words.data();
+        for (size_t r = 0; r < T; ++r)
+            for (uint32_t w = 0; w < W; ++w) dst[(size_t)w * T + r] = src[r * W + w];
+    }
+};
+
+// Records kept by index (a voice, an instrument, a kit's voice slot): of[i] = the first word of i's record in
+// `words`, or -1; `list`: the indices that have one.  Empty, it costs its users one test.
+struct KeptRecords {
+    uint32_t W = 0;
+    std::vector<int32_t> of;
+    std::vector<uint32_t> words, list;
+    void init(size_t count, uint32_t W_) { W = W_; of.assign(count, -1); words.clear(); list.clear(); }
+    const uint32_t *find(uint32_t i) const { return !list.empty() && of[i] >= 0 ? words.data() + of[i] : nullptr; }
+    void forget(uint32_t i) { if (!list.empty()) of[i] = -1; }
+    void forget_all() {
+        for (const uint32_t i : list) of[i] = -1;
+        list.clear();
+        words.clear();
+    }
+    // records [list_.size()][W] in order: the last record of an index stays
+    void keep(const std::vector<uint32_t> &list_, const std::vector<uint32_t> &words_) {
+        list = list_;
+        words = words_;
+        for (size_t r = 0; r < list.size(); ++r) of[list[r]] = (int32_t)(r * W);
+    }
+};
+
 // ---- sample voices: the bank's layout and each voice's Sample (olfx_sample_bank / olfx_sample_voices) ----
 // A validated bank: where each sample goes in the device allocation (kSmAlign-aligned starts, a
 // padded tail) and its frames.  n_samples = 0: no bank (floats = 0).
@@ -220,55 +267,43 @@ struct Shadow {
     int64_t n_components = 0;             // rack instances with OLFX_FR_TOPOLOGY >= 2
     bool pre_changed = true;              // a reverb pre-delay changed since the flag was last cleared
     std::vector<olfx_voice_event> events; // queued for the next block (its frame 0)
-    // olfx_timed_events: the events past frame 0, stably ordered by frame (frames count from the next block's
-    // first frame; an event at frame 0 goes to `events`, which keeps the queueing order across both calls)
-    // olfx_timed_notes (the synths and the drum kit, which take no timed voice events): the same list holds the
-    // pending instrument notes, unrouted -- ev.inst is the instrument, and the note is routed through Polyvoice /
-    // the VoiceMap when the engine reaches its frame (fold_segments, advance)
+    // The three pending lists: what the timed calls queued past frame 0, each stably ordered by frame in its queueing
+    // order (frames count from the next launch's first frame).  An entry at frame 0 never gets here: it is applied
+    // at the call, and one that reaches frame 0 in advance() is applied there.
+    // `timed`: olfx_timed_events, or olfx_timed_notes' instrument notes, unrouted -- ev.inst is the instrument, and the
+    // note is routed through Polyvoice / the VoiceMap when the engine reaches its frame (fold_segments, advance).
+    // `tparams`: olfx_timed_params / olfx_timed_control (the voice kinds) in one order for both calls; a control is
+    // held as the field and value it maps to (OLFX_FIELD_UPDATE_ONLY: Update() alone).
+    // `iparams`: olfx_timed_instrument_params / _control (the synths and the drum kit), raw, in one order for both.
     std::vector<olfx_timed_event> timed;
-    std::vector<olfx_voice_event> routed; // fold_segments: one segment's notes as voice events
-    // olfx_timed_params / olfx_timed_control (the voice kinds): the parameter records past frame 0, stably ordered
-    // by frame in one queueing order for both calls; a control is held as the field and value it maps to
-    // (OLFX_FIELD_UPDATE_ONLY: Update() alone).  A record at frame 0 is applied at the call and never listed.
     std::vector<olfx_timed_param> tparams;
-    // fold_segments: the launch's timed coefficient records -- the voice of each, segment by segment (segment s is
-    // tc_inst[tc_first[s] .. tc_first[s + 1])) and ascending inside a segment, and their words [records][VCC_N].
-    // The voices stay dirty: fill_records puts them back on the list, so their last record reaches the device
-    // arrays ahead of the next launch
-    std::vector<uint32_t> tc_inst, tc_first, tc_words;
-    bool tc_fresh = false;                // fold_segments made them and fill_records has yet to put the voices back
-    // ... and the dirty instances' records as frame 0 has them, derived before the timed records were applied
-    // ([m][words] in fill_records' order; valid for the fold's own fill_records)
-    std::vector<uint32_t> pre_words;
-    bool pre_valid = false;
-    // the last timed record of each voice the previous launch changed: its coefficient words as they stand until
-    // something writes to the voice again (mark_dirty forgets them), so the scatter ahead of the next launch
-    // derives nothing twice.  tc_cache_of[voice] = the record's first word in tc_cache, or -1
-    // tc_cached: the voices that have an entry (a packet without kept records touches none of this)
-    std::vector<int32_t> tc_cache_of;
-    std::vector<uint32_t> tc_cache, tc_cached;
-    // olfx_timed_instrument_params / olfx_timed_instrument_control (the synths and the drum kit): the records past
-    // frame 0, raw, stably ordered by frame in one queueing order for both calls
     std::vector<TimedInst> iparams;
-    // fold_segments: the launch's voice records -- the lane of each (a synth: the instrument; a kit: the device voice
-    // slot p * npad + kit), segment s being ti_vlane[ti_vfirst[s] .. ti_vfirst[s + 1]), ascending inside a segment,
-    // and their words [records][VCC_N] -- and its rack records likewise (lane = instrument, [records][TIF_N])
-    std::vector<uint32_t> ti_vlane, ti_vfirst, ti_vwords, ti_flane, ti_ffirst, ti_fwords;
-    // ... each rack record's whole FRC_N words, and during a fold an instrument's (a kit: voice slot hv's) latest voice
-    // record and an instrument's latest rack record (-1: none; all -1 between folds)
-    std::vector<uint32_t> ti_ffull;
-    std::vector<int32_t> ti_vlast, ti_flast;
-    // ... and what the launch's records changed: the instruments and (a kit) the voice slots hv = p * n + kit, each
-    // once, with the whole coefficient record of each as the launch's last time leaves it ([.][kd->words],
-    // [.][kd->vwords]).  fill_records puts them back on the dirty lists and keeps the records (ic_* / vc_*: as
-    // tc_cache, by instrument and by voice slot), so the scatter ahead of the next launch derives nothing twice;
-    // mark_dirty / mark_vdirty forget an entry.  A packet without such records touches none of this.
-    std::vector<uint32_t> ti_inst, ti_inst_words, ti_slot, ti_slot_words;
-    bool ti_fresh = false;
-    std::vector<int32_t> ic_of, vc_of;
-    std::vector<uint32_t> ic_words, ic_list, vc_words, vc_list;
-    // the dirty voice slots' records as frame 0 has them (a kit; pre_words' twin, [m2][vwords])
-    std::vector<uint32_t> pre_vwords;
+    std::vector<olfx_voice_event> routed; // fold_segments: one segment's notes as voice events
+    // fold_segments: the launch's timed coefficient records.  `vrec`: the voice records [VCC_N] -- a voice kind's lane
+    // is the voice, a synth's the instrument (the record reaches all its voices), a kit's the device voice slot
+    // p * npad + kit.  `frec`: an instrument's rack records [TIF_N], lane = instrument.  Both empty without a fold
+    // that had records.
+    SegRecords<VCC_N> vrec;
+    SegRecords<TIF_N> frec;
+    // ... the dirty records as frame 0 has them, derived before the fold applied anything ([m][words] and, a kit's
+    // voice slots, [m2][vwords], in fill_records' order; valid for the fold's own fill_records)
+    std::vector<uint32_t> pre_words, pre_vwords;
+    bool pre_valid = false;
+    // ... and whether the fold made records that fill_records has yet to put back on the dirty lists: what a launch's
+    // records change stays dirty, so its last record reaches the device arrays ahead of the next launch
+    bool fold_fresh = false;
+    // The last timed record of what the previous launch changed, so that the scatter ahead of the next launch derives
+    // nothing twice: a voice kind's voice words per voice, an instrument's whole record, a kit voice slot's whole
+    // record (hv = p * n + kit).  mark_dirty / mark_vdirty forget an entry, fill_records retires them all once they
+    // have served and keeps the fresh fold's.
+    KeptRecords kept_voice, kept_inst, kept_slot;
+    // an instrument fold's scratch: the lanes one time touches; each rack record's whole FRC_N words; an instrument's
+    // (a kit: voice slot hv's) latest voice record and an instrument's latest rack record (-1: none; all -1 between
+    // folds); and what the records changed -- the instruments and (a kit) the voice slots hv, each once, with the
+    // whole record of each as the launch's last time leaves it ([.][kd->words], [.][kd->vwords])
+    std::vector<uint32_t> at_v, at_f, rack_full;
+    std::vector<int32_t> last_v, last_f;
+    std::vector<uint32_t> changed_inst, changed_inst_words, changed_slot, changed_slot_words;
     // fold_events / fold_segments: one record per voice and segment, segment by segment and by first
     // appearance; segment s is folded[seg_first[s] .. seg_first[s + 1]) and starts at frame seg_frame[s]
     std::vector<Folded> folded;
@@ -377,16 +412,20 @@ struct Shadow {
     // segment per distinct frame of the timed events below `span`, which leave the pending list.  Instrument
     // notes are routed here, frame by frame in (frame, queueing order), against Playing() as the earlier frames
     // left it and the VoiceMap in force now; a segment whose notes were all dropped is an empty segment.
+    // The pending records below `span` (tparams, or iparams) are times too: each time's records land on the shadow
+    // ahead of its events and make that segment's coefficient records (vrec, frec).
     void fold_segments(uint32_t span_);
     uint32_t n_seg() const { return (uint32_t)seg_frame.size(); }
     // the launch's chunks (VoiceArgs::n_chunks): each segment's frames in chunks of `chunk`
     uint32_t n_chunks(uint32_t span_, uint32_t chunk) const;
     PacketPlan plan(bool evs) const {
+        const size_t nv = evs ? vrec.size() : 0u;         // a voice kind's section, or an instrument kind's
         return plan_packet(n, dirty_list.size(), kd->words, evs, n_more, n_ev(), vdirty_list.size(), kd->vwords,
-                           evs ? n_seg() : 1u, evs ? tc_inst.size() : 0u, evs ? ti_vlane.size() : 0u,
-                           evs ? ti_flane.size() : 0u, kit() ? voices * (npad >> 6) : npad >> 6, npad >> 6);
+                           evs ? n_seg() : 1u, instruments() ? 0u : nv, instruments() ? nv : 0u,
+                           evs ? frec.size() : 0u, kit() ? voices * (npad >> 6) : npad >> 6, npad >> 6);
     }
-    // The plan's instance list and field-major records into `buf`; clears the dirty list.
+    // The plan's instance list and field-major records into `buf`; clears the dirty lists, retires the kept
+    // records, and puts what a fold's records changed back on the lists with its last record kept.
     void fill_records(const PacketPlan &pl, uint32_t *buf);
     // The chorus kind: whether the next block runs the ring-free kernel -- the switch's state unless a
     // dirty instance's pitch or window words differ from the delivered ones (the words, not the call:
@@ -417,8 +456,8 @@ private:
         if (kit()) route_kit(to, ev.inst, ev.type, ev.note, ev.velocity);
         else route_synth(to, ev.inst, ev.type, ev.note, ev.velocity);
     }
-    // the pending list whose entries from `old` on are new: stably by frame, behind the queued ones of their frame
-    void merge_timed(size_t old);
+    // a timed call's frame check: OLFX_OK, or the refusal of entry k (`what`: "event" or "record") of `call`
+    int bad_frame(const char *call, const char *what, uint32_t k, uint32_t frame);
     // one segment's events onto `folded`, ev_count and ev_more; `coef`: the voices whose coefficients change at the
     // segment's start (VEV_COEF, alone or with the voice's events)
     void fold_one(const olfx_voice_event *ev, size_t count, size_t stride, const uint32_t *coef = nullptr, size_t n_coef = 0);
@@ -429,11 +468,16 @@ private:
     // validated instrument records: frame 0 now (set_range / control), the rest onto iparams
     void queue_inst(const std::vector<TimedInst> &recs);
     void apply_inst_now(const TimedInst &r);
-    // fold_segments: one record on params / configured at its frame without touching the dirty lists; the
-    // instruments it touched onto ti_inst, what needs a voice or rack record at this time onto at_v / at_f
-    void apply_inst_quiet(const TimedInst &r, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f);
-    void write_quiet(uint32_t inst, uint32_t field, float v, std::vector<uint32_t> &at_v, std::vector<uint32_t> &at_f);
-    void fold_instrument_segments(uint32_t span_);
+    // fold_segments: one record on params / configured at its frame without touching the dirty lists; what needs a
+    // voice or rack record at this time onto at_v / at_f, the instruments and kit voice slots it touched onto
+    // changed_inst / changed_slot
+    void apply_quiet(const olfx_timed_param &r);
+    void apply_quiet(const TimedInst &r);
+    void write_quiet(uint32_t inst, uint32_t field, float v);
+    // fold_segments over the pending records of the kind (tparams or iparams)
+    template <class R> void fold_with(std::vector<R> &pending, uint32_t span_);
+    // ... its tail for the instrument kinds: changed_inst / changed_slot, each once, with their whole last records
+    void keep_last_records();
     // fields [field0, field0 + n_fields) include a SynthVoice member (set_params implies Update())
     bool touches_voice(uint32_t field0, uint32_t n_fields) const {
         return kd->instances == KindDesc::VOICES || (n_fields && field0 < kd->voice_end && field0 + n_fields > kd->voice0);

@@ -131,13 +131,13 @@ TEST(TimedInstrumentParams, OneOrderForBothCallsAndParametersPrecedeNotes) {
     EXPECT_EQ(s.seg_frame[1], 8u);
     EXPECT_EQ(s.seg_frame[2], 16u);
     /* segment 1: instrument 5's voice record, as the parameter leaves it, and the note routed after it */
-    EXPECT_EQ(s.ti_vfirst[1], 0u);
-    EXPECT_EQ(s.ti_vfirst[2], 1u);
-    EXPECT_EQ(s.ti_vlane[0], 5u);
+    EXPECT_EQ(s.vrec.first[1], 0u);
+    EXPECT_EQ(s.vrec.first[2], 1u);
+    EXPECT_EQ(s.vrec.lane[0], 5u);
     EXPECT_EQ(param(s, 5, OLFX_SY_VOICE0 + OLFX_VC_AMP_ATTACK), 0.25f);
     EXPECT_EQ(s.configured[5], 1);
     const std::vector<uint32_t> w5 = voice_record(s, 5);
-    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.ti_vwords[k], w5[k]);
+    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.vrec.words[k], w5[k]);
     EXPECT_EQ(s.seg_first[2] - s.seg_first[1], 1u);
     EXPECT_EQ(s.folded[s.seg_first[1]].inst, 5u);            /* voice 0 of instrument 5 */
     EXPECT_EQ(s.playing[5], 64);
@@ -145,13 +145,13 @@ TEST(TimedInstrumentParams, OneOrderForBothCallsAndParametersPrecedeNotes) {
        at topology 1 reaches FILTER_CUTOFF): one voice record and one rack record for instrument 1 */
     EXPECT_EQ(param(s, 1, OLFX_SY_VOICE0 + OLFX_VC_FILTER_CUTOFF), 500.f);
     EXPECT_TRUE(param(s, 1, OLFX_SY_RACK0 + OLFX_FR_FILTER_CUTOFF) != rack_cutoff);
-    EXPECT_EQ(s.ti_vfirst[3], 2u);
-    EXPECT_EQ(s.ti_vlane[1], 1u);
-    EXPECT_EQ(s.ti_ffirst[2], 0u);
-    EXPECT_EQ(s.ti_ffirst[3], 1u);
-    EXPECT_EQ(s.ti_flane[0], 1u);
+    EXPECT_EQ(s.vrec.first[3], 2u);
+    EXPECT_EQ(s.vrec.lane[1], 1u);
+    EXPECT_EQ(s.frec.first[2], 0u);
+    EXPECT_EQ(s.frec.first[3], 1u);
+    EXPECT_EQ(s.frec.lane[0], 1u);
     const std::vector<uint32_t> f1 = rack_record(s, 1);
-    for (uint32_t k = 0; k < TIF_N; ++k) EXPECT_EQ(s.ti_fwords[k], f1[k]);
+    for (uint32_t k = 0; k < TIF_N; ++k) EXPECT_EQ(s.frec.words[k], f1[k]);
     EXPECT_EQ(s.iparams.size(), (size_t)1);
     EXPECT_EQ(s.iparams[0].frame, 72u);
     /* no record touched the dirty lists; fill_records puts the changed instruments back, each once */
@@ -214,7 +214,7 @@ TEST(TimedInstrumentParams, ControlMappedAtItsFrame) {
     EXPECT_EQ(pl.n_seg, (size_t)3);
     EXPECT_EQ(pl.n_iv, (size_t)1);
     EXPECT_EQ(u.configured[1 * u.n + 2], 1);
-    EXPECT_EQ(u.ti_vfirst.size(), (size_t)4);
+    EXPECT_EQ(u.vrec.first.size(), (size_t)4);
 }
 
 TEST(TimedInstrumentParams, CarryOverAndFrameZeroFirst) {
@@ -436,8 +436,8 @@ TEST(TimedInstrumentParams, SectionOffsetsTablesAndRecordsBySize) {
             EXPECT_EQ(pl.n_tc, (size_t)0);
             EXPECT_EQ(pl.gv, gv);
             EXPECT_EQ(pl.gf, G);
-            EXPECT_EQ(pl.n_iv, s.ti_vlane.size());
-            EXPECT_EQ(pl.n_if, s.ti_flane.size());
+            EXPECT_EQ(pl.n_iv, s.vrec.lane.size());
+            EXPECT_EQ(pl.n_if, s.frec.lane.size());
             EXPECT_EQ(pl.n_iv, (size_t)((n + 2) / 3) + (!kit && n > 40 ? 1u : 0u));
             EXPECT_EQ(pl.n_if, (size_t)std::min(n, 40u) + (n > 40 ? 1u : 0u));
             EXPECT_EQ(pl.o_ivt, up4(pl.o_seg + ((nseg + 1) & ~(size_t)1)));
@@ -468,12 +468,12 @@ TEST(TimedInstrumentParams, SectionOffsetsTablesAndRecordsBySize) {
                     }
                 EXPECT_EQ(seen, T);
             };
-            check(pl.o_ivt, gv, s.ti_vlane, s.ti_vfirst, pl.o_iv, VCC_N, s.ti_vwords);
-            check(pl.o_ift, G, s.ti_flane, s.ti_ffirst, pl.o_if, TIF_N, s.ti_fwords);
+            check(pl.o_ivt, gv, s.vrec.lane, s.vrec.first, pl.o_iv, VCC_N, s.vrec.words);
+            check(pl.o_ift, G, s.frec.lane, s.frec.first, pl.o_if, TIF_N, s.frec.words);
             /* the lanes: a synth's instrument, a kit's device voice slot p npad + kit; the records as the shadow has them */
-            EXPECT_TRUE(std::equal(lanes.begin(), lanes.end(), s.ti_vlane.begin()));
+            EXPECT_TRUE(std::equal(lanes.begin(), lanes.end(), s.vrec.lane.begin()));
             const std::vector<uint32_t> w0 = rack_record(s, n - 1);
-            for (uint32_t w = 0; w < TIF_N; ++w) EXPECT_EQ(s.ti_fwords[(s.ti_flane.size() - 1) * TIF_N + w], w0[w]);
+            for (uint32_t w = 0; w < TIF_N; ++w) EXPECT_EQ(s.frec.words[(s.frec.lane.size() - 1) * TIF_N + w], w0[w]);
         }
 }
 
@@ -503,7 +503,7 @@ TEST(TimedInstrumentParams, NoRecordNoChange) {
         EXPECT_EQ(pa.words, pb.words);
         EXPECT_TRUE(wa == wb);
         EXPECT_TRUE(a.dirty_list.empty() && a.vdirty_list.empty());
-        EXPECT_TRUE(a.ic_words.empty() && a.vc_words.empty() && a.ti_inst.empty() && a.ti_slot.empty() && !a.ti_fresh);
+        EXPECT_TRUE(a.kept_inst.words.empty() && a.kept_slot.words.empty() && a.changed_inst.empty() && a.changed_slot.empty() && !a.fold_fresh);
         /* ... and with nothing but the frame-0 write, the unsegmented packet */
         Shadow c = fresh(kind, 130), d = fresh(kind, 130);
         EXPECT_EQ(queue(c, {tp(0, 9, f, 700.f), tp(64, 9, f, 800.f)}), OLFX_OK);
@@ -543,15 +543,15 @@ TEST(TimedInstrumentParams, FrameZeroRecordsAndKeptRecords) {
         /* back on the lists with the last record kept; the next packet is what set_param of frame 8's values gives */
         EXPECT_EQ(s.dirty_list.size(), (size_t)1);
         EXPECT_EQ(s.vdirty_list.size(), (size_t)(kit ? 1 : 0));
-        EXPECT_TRUE(!s.ic_words.empty() && s.ic_of[7] == 0);
-        if (kit) EXPECT_TRUE(!s.vc_words.empty() && s.vc_of[2 * s.n + 7] == 0);
+        EXPECT_TRUE(!s.kept_inst.words.empty() && s.kept_inst.of[7] == 0);
+        if (kit) EXPECT_TRUE(!s.kept_slot.words.empty() && s.kept_slot.of[2 * s.n + 7] == 0);
         const float v8 = 4000.f, r8 = 0.25f;
         EXPECT_EQ(twin.set_range(7, 1, f, 1, &v8), OLFX_OK);
         EXPECT_EQ(twin.set_range(7, 1, rb, 1, &r8), OLFX_OK);
         EXPECT_EQ(launch(s, 64, &pl, &buf), 64u);
         EXPECT_EQ(launch(twin, 64, &pt, &tbuf), 64u);
         EXPECT_TRUE(buf == tbuf);
-        EXPECT_TRUE(s.ic_words.empty() && s.vc_words.empty() && s.dirty_list.empty() && s.vdirty_list.empty());
+        EXPECT_TRUE(s.kept_inst.words.empty() && s.kept_slot.words.empty() && s.dirty_list.empty() && s.vdirty_list.empty());
         /* a write after the launch forgets the kept record */
         EXPECT_EQ(queue(s, {tp(8, 7, f, 5000.f)}), OLFX_OK);
         EXPECT_EQ(launch(s, 64), 64u);

@@ -97,12 +97,12 @@ TEST(TimedParams, OrderByFrameThenArrival) {
     /* the last write of frame 16 on voice 1 wins; one record per voice and segment, by voice */
     EXPECT_EQ(param(s, 1, OLFX_VC_FILTER_CUTOFF), 500.f);
     const uint32_t want_tc[] = {2, 4, 1, 3};
-    EXPECT_EQ(s.tc_inst.size(), (size_t)4);
-    for (size_t k = 0; k < 4 && k < s.tc_inst.size(); ++k) EXPECT_EQ(s.tc_inst[k], want_tc[k]);
-    EXPECT_EQ(s.tc_first[0], 0u);
-    EXPECT_EQ(s.tc_first[1], 0u);
-    EXPECT_EQ(s.tc_first[2], 2u);
-    EXPECT_EQ(s.tc_first[3], 4u);
+    EXPECT_EQ(s.vrec.lane.size(), (size_t)4);
+    for (size_t k = 0; k < 4 && k < s.vrec.lane.size(); ++k) EXPECT_EQ(s.vrec.lane[k], want_tc[k]);
+    EXPECT_EQ(s.vrec.first[0], 0u);
+    EXPECT_EQ(s.vrec.first[1], 0u);
+    EXPECT_EQ(s.vrec.first[2], 2u);
+    EXPECT_EQ(s.vrec.first[3], 4u);
     EXPECT_EQ(s.tparams.size(), (size_t)1);
     EXPECT_EQ(s.tparams[0].frame, 72u);
     for (size_t k = 0; k < s.folded.size(); ++k) EXPECT_EQ(s.folded[k].op, (uint32_t)VEV_COEF);   /* VEV_COEF alone */
@@ -121,9 +121,9 @@ TEST(TimedParams, ParametersPrecedeEventsAtAFrame) {
     EXPECT_EQ(s.folded[0].op, (uint32_t)(VEV_COEF | VEV_GATE_SET | VEV_GATE_ON | VEV_RETRIGGER | VEV_FREQ));
     EXPECT_EQ(s.folded[1].inst, 6u);
     EXPECT_EQ(s.folded[1].op, (uint32_t)(VEV_GATE_SET | VEV_GATE_ON | VEV_RETRIGGER | VEV_FREQ));
-    EXPECT_EQ(s.tc_inst.size(), (size_t)1);
+    EXPECT_EQ(s.vrec.lane.size(), (size_t)1);
     const std::vector<uint32_t> w = record_of(s, 5);
-    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.tc_words[k], w[k]);
+    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.vrec.words[k], w[k]);
     /* a NoteOff after the change keeps the bit */
     Shadow t = fresh(OLFX_KIND_VOICE_SAMPLE, 70);
     EXPECT_EQ(queue(t, {tp(12, 9, OLFX_VC_FILTER_CUTOFF, 900.f)}), OLFX_OK);
@@ -221,11 +221,11 @@ TEST(TimedParams, TheKeptRecordIsTheOneScattered) {
         packet(s, 64, &pl);
         EXPECT_EQ(pl.n_tc, (size_t)4);
         EXPECT_EQ(s.dirty_list.size(), (size_t)3);
-        EXPECT_TRUE(s.tc_cache_of[3] >= 0 && s.tc_cache_of[5] >= 0 && s.tc_cache_of[69] >= 0 && s.tc_cache_of[4] < 0);
+        EXPECT_TRUE(s.kept_voice.find(3) != nullptr && s.kept_voice.find(5) != nullptr && s.kept_voice.find(69) != nullptr && s.kept_voice.find(4) == nullptr);
         s.advance(64);
         const float v = 0.9f;
         EXPECT_EQ(s.set_range(5, 1, OLFX_VC_PORTAMENTO, 1, &v), OLFX_OK);       /* voice 5: written again */
-        EXPECT_TRUE(s.tc_cache_of[5] < 0 && s.tc_cache_of[3] >= 0);
+        EXPECT_TRUE(s.kept_voice.find(5) == nullptr && s.kept_voice.find(3) != nullptr);
         const std::vector<uint32_t> dirty(s.dirty_list);
         const std::vector<uint32_t> buf = packet(s, 64, &pl);
         EXPECT_EQ(pl.n_seg, (size_t)1);
@@ -235,7 +235,7 @@ TEST(TimedParams, TheKeptRecordIsTheOneScattered) {
             EXPECT_EQ(buf[pl.o_inst + r], dirty[r]);
             for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(buf[pl.o_val + (size_t)k * m + r], w[k]);
         }
-        EXPECT_TRUE(s.dirty_list.empty() && s.tc_cache.empty() && s.tc_cached.empty() && s.tc_cache_of[3] < 0);
+        EXPECT_TRUE(s.dirty_list.empty() && s.kept_voice.words.empty() && s.kept_voice.list.empty() && s.kept_voice.find(3) == nullptr);
     }
 }
 
@@ -271,10 +271,10 @@ TEST(TimedParams, UpdateOnlyConfiguresAtItsFrame) {
     s.fold_segments(16);
     EXPECT_EQ(s.configured[2], 1);
     EXPECT_TRUE(s.params == p0);              /* members unchanged */
-    EXPECT_EQ(s.tc_inst.size(), (size_t)1);
+    EXPECT_EQ(s.vrec.lane.size(), (size_t)1);
     const std::vector<uint32_t> w1 = record_of(s, 2);
     EXPECT_TRUE(w0 != w1);                    /* Init's component defaults -> the members' */
-    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.tc_words[k], w1[k]);
+    for (uint32_t k = 0; k < VCC_N; ++k) EXPECT_EQ(s.vrec.words[k], w1[k]);
 }
 
 TEST(TimedParams, RefusedCallsChangeNothing) {
@@ -354,7 +354,7 @@ TEST(TimedParams, SpanCountsTheUnionOfTimes) {
     b.fold_segments(64);
     EXPECT_EQ(b.n_seg(), kSegCap);
     for (uint32_t k = 0; k < kSegCap; ++k) EXPECT_EQ(b.seg_frame[k], 4 * k);
-    EXPECT_EQ(b.tc_inst.size(), (size_t)8);
+    EXPECT_EQ(b.vrec.lane.size(), (size_t)8);
     EXPECT_EQ(b.n_chunks(64, 8), (uint32_t)kSegCap);
     b.advance(64);
     EXPECT_TRUE(b.tparams.empty() && b.timed.empty());
@@ -407,7 +407,7 @@ TEST(TimedParams, OffsetsAndBaseTableBySize) {
             EXPECT_EQ(s.span(64), 64u);
             host::PacketPlan pl;
             const std::vector<uint32_t> buf = packet(s, 64, &pl);
-            const size_t groups = (n + 63) / 64, T = s.tc_inst.size();
+            const size_t groups = (n + 63) / 64, T = s.vrec.lane.size();
             const size_t nseg = 3 + (n > third.size());
             EXPECT_EQ(pl.n_seg, nseg);
             EXPECT_EQ(T, (size_t)n);
@@ -419,7 +419,7 @@ TEST(TimedParams, OffsetsAndBaseTableBySize) {
             /* the base table restated: a segment's records by voice, a group's run where the lower groups' end */
             size_t before = 0;
             for (size_t sgm = 0; sgm < nseg; ++sgm) {
-                std::vector<uint32_t> in(s.tc_inst.begin() + s.tc_first[sgm], s.tc_inst.begin() + s.tc_first[sgm + 1]);
+                std::vector<uint32_t> in(s.vrec.lane.begin() + s.vrec.first[sgm], s.vrec.lane.begin() + s.vrec.first[sgm + 1]);
                 EXPECT_TRUE(std::is_sorted(in.begin(), in.end()));
                 for (size_t g = 0; g < groups; ++g) {
                     size_t lower = 0;
@@ -432,14 +432,14 @@ TEST(TimedParams, OffsetsAndBaseTableBySize) {
                     for (const uint32_t u : in) rank += (u >> 6) == (v >> 6) && u < v;
                     const size_t rec = base[sgm * groups + (v >> 6)] + rank;
                     EXPECT_TRUE(rec < T);
-                    EXPECT_EQ(s.tc_inst[rec], v);
-                    for (uint32_t w = 0; w < VCC_N; ++w) EXPECT_EQ(buf[pl.o_tc + (size_t)w * T + rec], s.tc_words[rec * VCC_N + w]);
+                    EXPECT_EQ(s.vrec.lane[rec], v);
+                    for (uint32_t w = 0; w < VCC_N; ++w) EXPECT_EQ(buf[pl.o_tc + (size_t)w * T + rec], s.vrec.words[rec * VCC_N + w]);
                 }
                 before += in.size();
             }
-            EXPECT_EQ(s.tc_first[1], 0u);
-            EXPECT_EQ((size_t)s.tc_first[2], third.size());
-            EXPECT_EQ(s.tc_first[3], s.tc_first[2]);
+            EXPECT_EQ(s.vrec.first[1], 0u);
+            EXPECT_EQ((size_t)s.vrec.first[2], third.size());
+            EXPECT_EQ(s.vrec.first[3], s.vrec.first[2]);
         }
 }
 
